@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the N2NMN CLEVR forward hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     (N > 1: the script re-executes itself under torch.distributed.run, one rank per GPU; when the
      driver already launched it that way, RANK / LOCAL_RANK / WORLD_SIZE come from the environment)
 
@@ -27,11 +27,14 @@ one GPU, so the driver's default line carries them too (`--config 4|5|6` runs th
 
 Inputs are resident in HBM before the timed region.  Multi-GPU: the path shards by question with no
 data-path collective (weak scaling: every rank runs its own stream of batches); timing =
-barrier + synchronize on both sides, max over ranks.  The block of `--steps` passes is repeated until
-the blocks span 0.3 s (at least three) and the median block is reported (`timed_region_s`, `repeats`,
-`blocks_s`, `value_min_max`).
+barrier + synchronize on both sides, max over ranks (`timed_region_s`).
 
-Prints ONE JSON line on rank 0.
+`--dump-outputs DIR`: after the timed passes, what the last timed pass of every worker handed its caller
+(answer logits, layout tokens, layout validity) is written as DIR/<name>.npy (float32; rank 0).  The
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
+
+Prints ONE JSON line on rank 0: the headline figures and a summary of every sub-report (result_line);
+the full report, per-kernel tables included, goes to stderr as one JSON line.
 """
 import argparse
 import json
@@ -88,6 +91,9 @@ def parse():
                     help="ground-truth layout mix of the timed passes ('clevr_like': synth.clevr_like_layout_batch)")
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-profile', action='store_true')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed passes, write what the last timed pass of every worker computed '
+                         '(scores, tokens, validity; rank 0) as DIR/<name>.npy (--config 2 / 3)')
     return ap.parse_args()
 
 
@@ -242,7 +248,7 @@ def bench_train(args, dp, local_rank):
     out = train_numbers(args, dp, local_rank, args.steps, args.warmup, not args.no_profile,
                         not args.no_cpu_baseline)
     if dp.rank == 0:
-        emit_line(json.dumps(out))
+        emit_report(out)
     dp.close()
 
 
@@ -360,7 +366,7 @@ def bench_vqa(args, dp, local_rank):
             out['passes_device_layouts'] = {k: pd[k] for k in ('value', 'ms_per_step', 'steps', 'host_sync', 'kernels')
                                             if k in pd}
     if dp.rank == 0:
-        emit_line(json.dumps(out))
+        emit_report(out)
     dp.close()
 
 
@@ -527,7 +533,7 @@ def bench_vqa_train(args, dp, local_rank):
             rows = kernel_rows(eng.engine.profile_end(), ksteps)
             out['kernels'] = rows
             out['gpu_us_per_step'] = round(sum(r['us_per_step'] for r in rows), 1)
-        emit_line(json.dumps(out))
+        emit_report(out)
     dp.close()
 
 
@@ -582,18 +588,63 @@ def ensure_world(args, argv):
     os.execvp(cmd[0], cmd)
 
 
-def timed_blocks(dp, run, sync, min_window_s=0.3, max_repeats=15):
-    """dp.timed(run) -- exactly `--steps` steps between barrier + synchronize -- is one BLOCK.  A single
-    short block (20 passes = 68 ms) is too noisy to headline, so blocks are repeated until at least
-    three have run and together they span min_window_s; the MEDIAN block is reported, with the
-    fastest and the slowest beside it.  Returns (median seconds, repeats, all blocks)."""
-    blocks = [dp.timed(run, sync)]
-    while len(blocks) < max_repeats and (len(blocks) < 3 or sum(blocks) < min_window_s):
-        if blocks[0] >= min_window_s and len(blocks) >= 1:
-            break                                  # one block is already a long window
-        blocks.append(dp.timed(run, sync))
-    s = sorted(blocks)
-    return s[len(s) // 2], len(blocks), blocks
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, pipe, steps):
+    """--dump-outputs: what the last timed pass of every worker that ran one handed its caller -- answer
+    logits [R, C], layout tokens [T_dec, R], layout validity [R], the workers' rows one after the other --
+    as DIR/<name>.npy in float32.  Past DUMP_LIMIT_BYTES a fixed, seeded sample of the rows is written,
+    its row indices in DIR/rows.npy.  Returns the names written."""
+    import numpy as np
+    sc, tk, va = [], [], []
+    for si, wk in enumerate(pipe.workers):
+        if steps // pipe.S + (1 if si < steps % pipe.S else 0) == 0:
+            continue                               # (fewer timed passes than workers)
+        b = wk['buckets'][(wk['next'] - 1) % 2]
+        sc.append(b.scores.cpu().numpy())
+        tk.append(b.tokens.cpu().numpy())
+        va.append(b.validity.cpu().numpy())
+    out = {'scores': np.concatenate(sc, 0), 'tokens': np.concatenate(tk, 1), 'validity': np.concatenate(va, 0)}
+    out = {k: v.astype(np.float32) for k, v in out.items()}
+    rows = out['validity'].shape[0]
+    per_row = sum(v.nbytes for v in out.values()) / rows
+    if per_row * rows > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(rows, int(DUMP_LIMIT_BYTES // (per_row + 8)), replace=False))
+        out = {'scores': out['scores'][keep], 'tokens': out['tokens'][:, keep], 'validity': out['validity'][keep],
+               'rows': keep.astype(np.float64)}
+    os.makedirs(directory, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(directory, k + '.npy'), v)
+    return sorted(out)
+
+
+# the result line keeps these sub-reports whole, and of every other one the figures named in LINE_FIGURES
+LINE_WHOLE = ('config', 'parity_check', 'roofline', 'cpu_baseline')
+LINE_FIGURES = ('value', 'unit', 'ms_per_step', 'ok', 'max_abs_logit_err', 'byte_weighted')
+
+
+def result_line(out):
+    """The stdout line: the report's scalars, LINE_WHOLE, and of every other sub-report its LINE_FIGURES plus
+    value / ms_per_step of the members that carry a value.  Per-kernel tables and notes stay in the full
+    report (stderr): the line stays a few KB, so a reader that keeps only the tail of stdout gets all of it."""
+    line = {}
+    for k, v in out.items():
+        if k in LINE_WHOLE or not isinstance(v, (dict, list)):
+            line[k] = v
+        elif isinstance(v, dict):
+            sub = {f: v[f] for f in LINE_FIGURES if f in v}
+            sub.update({m: {f: x[f] for f in ('value', 'ms_per_step') if f in x}
+                        for m, x in v.items() if isinstance(x, dict) and 'value' in x})
+            line[k] = sub
+    return line
+
+
+def emit_report(out):
+    """the full report to stderr, the result line to stdout (one JSON line each)"""
+    sys.stderr.write('bench.py full report: %s\n' % json.dumps(out))
+    sys.stderr.flush()
+    emit_line(json.dumps(result_line(out)))
 
 
 def nesting_histogram(tokens, names):
@@ -641,6 +692,8 @@ def main():
     elif args.eos_retire or args.layouts != 'templates':
         sys.exit('bench.py: --eos-retire / --layouts are for --plain runs (tracing); the default line carries '
                  'the option and both mixes under its `eos_retire` key')
+    if args.dump_outputs and args.config not in (2, 3):
+        sys.exit('bench.py: --dump-outputs writes the outputs of the forward passes (--config 2 / 3)')
     ensure_world(args, sys.argv[1:])
     own_stdout()
     import numpy as np
@@ -699,8 +752,10 @@ def main():
 
     sync = lambda: torch.cuda.synchronize(dev)    # noqa: E731
     run_steps(max(args.warmup, 2 * S))
-    elapsed, repeats, blocks = timed_blocks(dp, lambda: run_steps(args.steps), sync)
-    fastest_rank_s = getattr(dp, 'last_min_elapsed', elapsed)      # (of the last block)
+    elapsed = dp.timed(lambda: run_steps(args.steps), sync)        # exactly `--steps` passes
+    fastest_rank_s = getattr(dp, 'last_min_elapsed', elapsed)
+    if rank == 0 and args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, pipe, args.steps)
     out = None
     if rank == 0:
         qps = dp.throughput(K * d.N * args.steps, elapsed)
@@ -714,34 +769,30 @@ def main():
             'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
             'dtype': 'f32' if pipe.mode != 'throughput_bf16x3' else 'bf16x3 (fp32-equivalent split operands)',
             'data': 'synthetic',
-            'timed_region_s': round(elapsed, 5), 'repeats': repeats,
-            'blocks_s': [round(x, 5) for x in blocks],
-            'timed_window_s': round(sum(blocks), 4),
-            'value_min_max': [round(dp.throughput(K * d.N * args.steps, max(blocks)), 1),
-                              round(dp.throughput(K * d.N * args.steps, min(blocks)), 1)],
+            'timed_region_s': round(elapsed, 5),
+            'dump_outputs': '%s: %s' % (args.dump_outputs, ', '.join(dumped)) if args.dump_outputs else None,
             'config': {'workload': 'BASELINE.json configs[%d]: CLEVR forward, %s layouts, 10x15x512 feats, '
                                    '%d x batch %d per pass, %d streams' %
                                    (args.config - 1, 'gt' if use_gt else 'greedy-decoder', K, d.N, S),
                        'note': 'client batches of %d questions, synthetic pool5, T_enc=45, T_dec=20; one '
                                'step = ONE PASS of the hot path over %d client batches (%d questions: they '
                                'share every launch); %d passes in flight on %d streams, each stream '
-                               'alternating two buckets of distinct inputs; `value` = median of `repeats` '
-                               'blocks of exactly `steps` passes (`value_min_max` = slowest / fastest '
-                               'block); layouts: %s; the strict one-batch-in-flight figure is '
-                               '`single_batch`' %
+                               'alternating two buckets of distinct inputs; `value` = exactly `steps` '
+                               'passes in one timed region; layouts: %s; the strict one-batch-in-flight '
+                               'figure is `single_batch`' %
                                (d.N, K, K * d.N, S, S,
                                 'fixed ground-truth layouts (10-template mix, teacher-forced decoder)'
                                 if use_gt else 'chosen by the greedy seq2seq decoder'),
                        'client_batch': d.N, 'batches_per_pass': K, 'rows_per_launch': K * d.N,
                        'questions_per_step': K * d.N, 'global_batch': world * K * d.N,
                        'streams_per_gpu': S, 'questions_in_flight': S * K * d.N,
-                       'passes_per_stream_per_block': args.steps // S,
+                       'passes_per_stream': args.steps // S,
                        'lstm_step_mode': pipe.mode, 'eos_retire': bool(pipe.eos_retire), 'layout_mix': args.layouts,
                        'parallelism': 'dp%d (question-sharded, no data-path collective)' % world,
                        # multi-GPU readiness: ranks the process group holds (not the --gpus asked for) and
-                       # the slowest / fastest rank's own rate in the last timed block
+                       # the slowest / fastest rank's own rate in the timed region
                        'ranks_in_group': dp.group_size(), 'gpus_requested': args.gpus,
-                       'per_rank_value_min_max': [round(K * d.N * args.steps / max(blocks[-1], 1e-9), 1),
+                       'per_rank_value_min_max': [round(K * d.N * args.steps / max(elapsed, 1e-9), 1),
                                                   round(K * d.N * args.steps / max(fastest_rank_s, 1e-9), 1)],
                        'host_sync': 'none: layouts are decoded on the device by the walker'
                        if not args.host_assemble else 'predicted_tokens D2H + C++ assembler'},
@@ -821,7 +872,7 @@ def main():
         if use_gt:
             t3 = wall(one_greedy, n1)
             eng.set_mode(pipe.mode)
-            # (blocks of `steps` passes like the headline: a call per pass would put the workers' hand-over
+            # (runs of `steps` passes like the headline: a call per pass would put the workers' hand-over
             # between every two passes)
             npass = max(args.steps, 2 * S)
             t_est = wall(lambda: run_steps(npass, gt=False), 1, warm=1)
@@ -1229,7 +1280,7 @@ def main():
 
     pipe.close()
     if rank == 0:
-        emit_line(json.dumps(out))
+        emit_report(out)
     dp.close()
 
 

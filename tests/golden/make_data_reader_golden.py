@@ -4,7 +4,9 @@
 _run_prefetch, imported from the checkout) produce on the synthetic imdbs of data_reader_cases.py.
 Only runs where /root/reference exists.  Two shims for today's numpy, neither touching the logic:
 the imdb is handed over as a list (np.load of a pickled object array needs allow_pickle=True, which
-the reference's DataReader.__init__ does not pass) and `np.bool` is aliased to `bool`."""
+the reference's DataReader.__init__ does not pass) and `np.bool` is aliased to `bool`.
+
+    python tests/golden/make_data_reader_golden.py [OUT]      (OUT: default, the committed golden)"""
 import json
 import os
 import queue
@@ -68,7 +70,7 @@ def assembler_for(variant, extra):
     return Assembler(os.path.join(REF, 'exp_vqa/data/vocabulary_layout.txt'))
 
 
-def main():
+def main(path=os.path.join(HERE, 'data_reader_golden.json')):
     gold = {}
     with tempfile.TemporaryDirectory() as tmp:
         for name, variant, rk, extra in DC.CASES:
@@ -77,11 +79,10 @@ def main():
             bs = reference_batches(variant, imdb, params, rk['shuffle'], rk['one_pass'], seed=11)
             gold[name] = DC.digest(bs)
             print(name, len(bs), 'batches')
-    path = os.path.join(HERE, 'data_reader_golden.json')
     with open(path, 'w') as f:
         json.dump(gold, f, indent=0, sort_keys=True)
     print('wrote', path)
 
 
 if __name__ == '__main__':
-    main()
+    main(*sys.argv[1:2])

@@ -56,3 +56,68 @@ def test_stdout_carries_only_the_result_line():
     assert r.returncode == 0, r.stderr
     assert r.stdout == '{"value": 1}\n'
     assert 'library noise' in r.stderr and 'raw noise on fd 1' in r.stderr
+
+
+def test_result_line_fits_a_short_stdout_tail():
+    """The full report of a default run (profiles/r06_bench_steps20.json, 22 KB) goes to stderr; the stdout line
+    keeps the headline, `config`, `parity_check`, `roofline`, `cpu_baseline` and the figures of every sub-report
+    in a few KB."""
+    import json
+    import bench
+    with open(os.path.join(ROOT, 'profiles', 'r06_bench_steps20.json')) as f:
+        full = json.load(f)
+    line = bench.result_line(full)
+    assert len(json.dumps(line)) <= 6000
+    for k in ('metric', 'value', 'unit', 'steps', 'ms_per_step', 'config', 'parity_check', 'roofline', 'cpu_baseline'):
+        assert line[k] == full[k], k
+    assert line['config4']['value'] == full['config4']['value']
+    assert line['config5']['passes']['value'] == full['config5']['passes']['value']
+    assert line['roofline_attention']['byte_weighted'] == full['roofline_attention']['byte_weighted']
+    assert 'kernels' not in line
+
+
+def _fake_pipe(S, rows, T, C, passes_per_worker):
+    """PassPipeline's worker records as dump_outputs reads them: bucket (next - 1) % 2 holds the last pass"""
+    import torch
+    workers = []
+    for si in range(S):
+        buckets = []
+        for j in range(2):
+            b = types.SimpleNamespace()
+            b.scores = torch.full((rows, C), 10.0 * si + j)
+            b.tokens = torch.full((T, rows), si * 2 + j, dtype=torch.int32)
+            b.validity = torch.ones(rows, dtype=torch.int32)
+            buckets.append(b)
+        workers.append({'buckets': buckets, 'next': passes_per_worker[si]})
+    return types.SimpleNamespace(S=S, workers=workers)
+
+
+def test_dump_outputs_writes_the_last_pass_of_every_worker(tmp_path):
+    import numpy as np
+    import bench
+    pipe = _fake_pipe(2, 8, 5, 3, [4, 3])            # 7 timed passes: worker 0 ends on bucket 1, worker 1 on 0
+    names = bench.dump_outputs(str(tmp_path), pipe, 7)
+    assert names == ['scores', 'tokens', 'validity']
+    sc, tk, va = (np.load(str(tmp_path / (n + '.npy'))) for n in names)
+    assert sc.dtype == tk.dtype == va.dtype == np.float32
+    assert sc.shape == (16, 3) and tk.shape == (5, 16) and va.shape == (16,)
+    assert (sc[:8] == 1.0).all() and (sc[8:] == 10.0).all()
+    assert (tk[:, :8] == 1).all() and (tk[:, 8:] == 2).all()
+    # one timed pass: only worker 0 ran one
+    names = bench.dump_outputs(str(tmp_path / 'one'), _fake_pipe(2, 8, 5, 3, [1, 0]), 1)
+    assert np.load(str(tmp_path / 'one' / 'scores.npy')).shape == (8, 3)
+
+
+def test_dump_outputs_samples_rows_past_the_limit(tmp_path, monkeypatch):
+    import numpy as np
+    import bench
+    monkeypatch.setattr(bench, 'DUMP_LIMIT_BYTES', 4096)
+    pipe = _fake_pipe(1, 256, 5, 3, [1])             # 256 rows x 36 B > 4 KB
+    names = bench.dump_outputs(str(tmp_path / 'a'), pipe, 1)
+    assert names == ['rows', 'scores', 'tokens', 'validity']
+    total = sum(np.load(str(tmp_path / 'a' / (n + '.npy'))).nbytes for n in names)
+    assert total <= 4096
+    rows = np.load(str(tmp_path / 'a' / 'rows.npy'))
+    assert rows.dtype == np.float64 and (np.diff(rows) > 0).all()
+    bench.dump_outputs(str(tmp_path / 'b'), pipe, 1)  # the sample is fixed
+    assert np.array_equal(rows, np.load(str(tmp_path / 'b' / 'rows.npy')))
