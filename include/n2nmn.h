@@ -65,7 +65,7 @@ typedef struct {
   int32_t T_decoder;          /* 20  maximum decoder length */
   int32_t N;                  /* 64  maximum batch size */
   int32_t kernel_size;        /* 5   TransformModule conv kernel */
-  int32_t variant;            /* N2NMN_VARIANT_CLEVR (models_clevr) or N2NMN_VARIANT_VQA (models_vqa) */
+  int32_t variant;            /* N2NMN_VARIANT_CLEVR (models_clevr), _VQA (models_vqa) or _SHAPES (models_shapes) */
   int32_t qpn_hidden;         /* VQA: hidden width of question_prior_net (500), 0 = use_qpn False */
 } n2nmn_dims;
 
@@ -77,6 +77,14 @@ typedef struct {
  * plus the question prior network.  Other operator codes are rejected (N2NMN_EKEY). */
 #define N2NMN_VARIANT_CLEVR 0
 #define N2NMN_VARIANT_VQA   1
+/* models_shapes (exp_shapes/train_shapes_gt_layout.py): the CLEVR operator kernels for _Find,
+ * _Transform, _And and _Answer (= N2NMN_OP_EXIST's arithmetic), a decoder without a validity
+ * automaton and with the <eos> latch (models_shapes/nmn3_netgen_att.py:211-222), and shapes_convnet
+ * (models_shapes/shapes_convnet.py:8-17: 10x10 stride-10 VALID conv 3 -> 64 + ReLU, 1x1 conv
+ * 64 -> D + ReLU) inside the training step.  The variable table holds exactly the models_shapes
+ * variables: the seq2seq, FindModule, TransformModule, ExistModule (the reference's AnswerModule)
+ * and neural_module_network/image_feature_cnn/shapes_convnet/conv_{1,2}/{weights,biases}. */
+#define N2NMN_VARIANT_SHAPES 2
 
 const char *n2nmn_last_error(void);
 const char *n2nmn_version(void);
@@ -451,7 +459,10 @@ typedef struct {
   const int32_t *seq_length;       /* [N]                                                    */
   int32_t T_enc, N, T_dec;
   const int32_t *gt_layout;        /* [T_dec, N] ground-truth layout tokens                  */
-  const float *image_feat;         /* [N, H, W, D]                                           */
+  const float *image_feat;         /* [N, H, W, D]; N2NMN_VARIANT_SHAPES: the mean-subtracted
+                                      image batch [N, 10H, 10W, 3] -- the step runs
+                                      shapes_convnet on it, trains its four variables, and
+                                      computes no gradient with respect to the images          */
   const int32_t *answer_labels;    /* [N]                                                    */
   float weight_decay;              /* 5e-6 (train_clevr_gt_layout.py:39)                     */
   /* outputs */
@@ -481,7 +492,10 @@ typedef struct {
    * OUTPUT of every LSTM layer but the last; models_vqa/question_prior_net.py:22-26).  TF draws the
    * masks from its own RNG stream; here they are inputs: float MULTIPLIERS, 0 for a dropped element
    * and 1 / keep_prob (= 2) for a kept one (n2nmn_dropout_multipliers fills such a buffer from a
-   * counter-based generator).  NULL = that dropout is off.  Row order: the batch's own. */
+   * counter-based generator).  NULL = that dropout is off.  Row order: the batch's own.
+   * N2NMN_VARIANT_SHAPES takes drop_enc0 / drop_dec0 as well (train_shapes_gt_layout.py:31-32); in
+   * its teacher-forced loss the steps behind a row's first <eos> count log 1 = 0 and get no
+   * gradient (the <eos> step itself counts). */
   const float *drop_enc0;          /* [T_enc, N, lstm_dim]: encoder LSTM layer 0 -> layer 1   */
   const float *drop_dec0;          /* [T_dec, N, lstm_dim]: decoder LSTM layer 0 -> layer 1   */
   const float *drop_qpn_h;         /* [N, 2 * lstm_dim]: question_prior_net input h_concat    */
@@ -533,7 +547,8 @@ int n2nmn_train_reset_optimizer(n2nmn_ctx *ctx, n2nmn_stream stream);
 int n2nmn_get_weight(n2nmn_ctx *ctx, const char *name, float *out, n2nmn_stream stream);
 /* debug / parity: copy an internal gradient tensor ("d_word_vecs" [T_dec,N,E], "d_token_scores"
  * [T_dec,N,16], "d_encoder_outputs" [T_enc,N,L], "d_encoder_h_transformed" [T_enc,N,L],
- * "d_scores" [N,C]) into `out` (device, capacity in floats); returns the element count */
+ * "d_scores" [N,C], "token_scores" [T_dec,N,V] (the forward's token logits), N2NMN_VARIANT_SHAPES: "d_image_feat" [N,H,W,D], the gradient arriving at
+ * shapes_convnet's output) into `out` (device, capacity in floats); returns the element count */
 int64_t n2nmn_train_debug_tensor(n2nmn_ctx *ctx, const char *name, float *out, int64_t capacity,
                                  n2nmn_stream stream);
 

@@ -77,6 +77,8 @@ static void build_vars(n2nmn_ctx* c) {
   add_var(c, lstm(dec, 1, "weights"), {2 * L, 4 * L});
   add_var(c, lstm(dec, 1, "biases"), {4 * L});
   const bool vqa = d.variant == N2NMN_VARIANT_VQA;
+  // models_shapes: Find, Transform, And and Answer (ExistModule's variables) only
+  const bool shapes = d.variant == N2NMN_VARIANT_SHAPES;
   auto layer = [&](const char* scope, const char* name, std::vector<int64_t> shape,
                    bool present = true) {
     const int64_t out = shape.back();
@@ -89,25 +91,26 @@ static void build_vars(n2nmn_ctx* c) {
   // models_vqa: the three-way product module is called TransformModule
   // (models_vqa/nmn3_modules.py:123-171); it occupies the FindSameProperty slots
   const char* fsp = vqa ? "TransformModule" : "FindSamePropertyModule";
-  layer(fsp, "conv_image", {D, M});
-  layer(fsp, "fc_text", {E, M});
-  layer(fsp, "fc_att", {D, M});
-  layer(fsp, "conv_eltwise", {M, 1});
+  layer(fsp, "conv_image", {D, M}, !shapes);
+  layer(fsp, "fc_text", {E, M}, !shapes);
+  layer(fsp, "fc_att", {D, M}, !shapes);
+  layer(fsp, "conv_eltwise", {M, 1}, !shapes);
   layer("TransformModule", "conv_maps", {ks, ks, 1, M}, !vqa);
   layer("TransformModule", "text_fc", {E, M}, !vqa);
   layer("TransformModule", "conv_eltwise", {M, 1}, !vqa);
   layer("ExistModule", "fc_scores", {3, C}, !vqa);
-  layer("CountModule", "fc_scores", {HW + 2, C}, !vqa);
-  layer("EqualNumModule", "fc_scores", {2 * HW + 4, C}, !vqa);
-  layer("MoreNumModule", "fc_scores", {2 * HW + 4, C}, !vqa);
-  layer("LessNumModule", "fc_scores", {2 * HW + 4, C}, !vqa);
-  layer("SamePropertyModule", "fc_text", {E, M}, !vqa);
-  layer("SamePropertyModule", "fc_att_0", {D, M}, !vqa);
-  layer("SamePropertyModule", "fc_att_1", {D, M}, !vqa);
-  layer("SamePropertyModule", "fc_eltwise", {M, C}, !vqa);
-  layer("DescribeModule", "fc_text", {E, M});
-  layer("DescribeModule", "fc_att", {D, M});
-  layer("DescribeModule", "fc_eltwise", {M, C});
+  const bool clevr = d.variant == N2NMN_VARIANT_CLEVR;
+  layer("CountModule", "fc_scores", {HW + 2, C}, clevr);
+  layer("EqualNumModule", "fc_scores", {2 * HW + 4, C}, clevr);
+  layer("MoreNumModule", "fc_scores", {2 * HW + 4, C}, clevr);
+  layer("LessNumModule", "fc_scores", {2 * HW + 4, C}, clevr);
+  layer("SamePropertyModule", "fc_text", {E, M}, clevr);
+  layer("SamePropertyModule", "fc_att_0", {D, M}, clevr);
+  layer("SamePropertyModule", "fc_att_1", {D, M}, clevr);
+  layer("SamePropertyModule", "fc_eltwise", {M, C}, clevr);
+  layer("DescribeModule", "fc_text", {E, M}, !shapes);
+  layer("DescribeModule", "fc_att", {D, M}, !shapes);
+  layer("DescribeModule", "fc_eltwise", {M, C}, !shapes);
   // models_vqa/question_prior_net.py:10-28 (scope neural_module_network/question_prior_net)
   const bool qpn = vqa && d.qpn_hidden > 0;
   const int64_t Hq = d.qpn_hidden > 0 ? d.qpn_hidden : 1;
@@ -116,6 +119,12 @@ static void build_vars(n2nmn_ctx* c) {
   add_var(c, q + "fc1/biases", {Hq}, qpn);
   add_var(c, q + "fc2/weights", {Hq, C}, qpn);
   add_var(c, q + "fc2/biases", {C}, qpn);
+  // models_shapes/shapes_convnet.py:8-17 (scope neural_module_network/image_feature_cnn/shapes_convnet)
+  const std::string cnn = "neural_module_network/image_feature_cnn/shapes_convnet/";
+  add_var(c, cnn + "conv_1/weights", {SHAPES_PATCH, SHAPES_PATCH, 3, SHAPES_C1}, shapes);
+  add_var(c, cnn + "conv_1/biases", {SHAPES_C1}, shapes);
+  add_var(c, cnn + "conv_2/weights", {1, 1, SHAPES_C1, D}, shapes);
+  add_var(c, cnn + "conv_2/biases", {D}, shapes);
 }
 
 static size_t carve_weights(n2nmn_ctx* c, char* base) {
@@ -1308,8 +1317,8 @@ int n2nmn_ctx_create(const n2nmn_dims* dims, int device, n2nmn_ctx** out) {
              "ctx_create: embed dims must be equal multiples of 4");
   N2_REQUIRE(d.D % (4 * POOL_PARTS) == 0 && d.D <= 4096, N2NMN_EINVAL,
              "ctx_create: D must be a multiple of 16, at most 4096");
-  N2_REQUIRE(d.variant == N2NMN_VARIANT_CLEVR || d.variant == N2NMN_VARIANT_VQA, N2NMN_EINVAL,
-             "ctx_create: unknown model variant");
+  N2_REQUIRE(d.variant == N2NMN_VARIANT_CLEVR || d.variant == N2NMN_VARIANT_VQA ||
+                 d.variant == N2NMN_VARIANT_SHAPES, N2NMN_EINVAL, "ctx_create: unknown model variant");
   N2_REQUIRE(d.qpn_hidden >= 0 && (d.qpn_hidden == 0 || d.variant == N2NMN_VARIANT_VQA),
              N2NMN_EINVAL, "ctx_create: qpn_hidden is a models_vqa option");
   N2_REQUIRE(d.map_dim <= 1024, N2NMN_EINVAL, "ctx_create: map_dim must be <= 1024");
@@ -1612,7 +1621,7 @@ extern "C++" int n2nmn::commit_weights_on(n2nmn_ctx* c, hipStream_t s, hipStream
     pr.tiles(m(V_ATT_W), L, 0, L, L / 16, 0, c->att_W_t);
     pr.pk(m(V_ATT_W), L, L, L, c->att_W_p, c->KpL, L);
     pr.pk(m(V_FIND_IMG_W), M, d.D, M, c->find_img_p, c->KpD, Mp);
-    pr.pk(m(V_FSP_IMG_W), M, d.D, M, c->fsp_img_p, c->KpD, Mp);
+    if (has(V_FSP_IMG_W)) pr.pk(m(V_FSP_IMG_W), M, d.D, M, c->fsp_img_p, c->KpD, Mp);
     pr.pad(m(V_DEC_EMB), V, E, c->dec_emb_cat, E);
     pr.pad(m(V_DEC_GO), 1, E, c->dec_emb_cat + (size_t)V * E, E);
     // zero-padded copies of the [M] vectors / [.., M] matrices read with float4 lanes

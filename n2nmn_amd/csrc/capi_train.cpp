@@ -31,6 +31,12 @@ struct TrainState {
         *dctx = nullptr, *dq = nullptr, *dout = nullptr, *dvp = nullptr, *deht = nullptr,
         *denc_out = nullptr;
   float *dz0_all = nullptr, *dz1_all = nullptr;     // encoder: dz of every step, row-major
+  // models_shapes: shapes_convnet inside the step.  Rows are feature-grid pixels (n, i, j) in image order
+  // (forward) or in the Find image-slot order of the program (backward: slot q holds image tab[q])
+  float *cnn_patches = nullptr, *cnn_c1 = nullptr, *cnn_feat = nullptr;   // [N*HW][300], [N*HW][64], [N*HW][D]
+  float *cnn_dfeat = nullptr, *cnn_dz2 = nullptr, *cnn_dc1 = nullptr;     // slot rows: [.][D], [.][D], [.][64]
+  float *cnn_dfeat_img = nullptr;     // [N*HW][D] d image_feat_grid in image order (zero block; debug / parity)
+  float *cnn1_p = nullptr, *cnn2_p = nullptr, *find_imgT_p = nullptr, *cnn2T_p = nullptr;   // PK packs
   // the decoder's own (its weight-gradient GEMMs read them on the side stream while the encoder's
   // reverse-time pass is already writing dz0_all / dz1_all)
   float *ddz0_all = nullptr, *ddz1_all = nullptr;
@@ -164,7 +170,9 @@ size_t carve_train(n2nmn_ctx* c, TrainState* t, char* base) {
   r.dc0s = k.take<float>((Td + 1) * N * L); r.dc1s = k.take<float>((Td + 1) * N * L);
   r.dh0s = k.take<float>((Td + 1) * N * L); r.dh1s = k.take<float>((Td + 1) * N * L);
   r.ctx = k.take<float>(Td * N * L);
-  if (d.variant == N2NMN_VARIANT_VQA) {      // dropout on LSTM layer 0's output (models_vqa training)
+  const bool shapes = d.variant == N2NMN_VARIANT_SHAPES;
+  // dropout on LSTM layer 0's output (models_vqa and models_shapes training)
+  if (d.variant == N2NMN_VARIANT_VQA || shapes) {
     r.eh0d = k.take<float>(T * N * L);
     r.dh0d = k.take<float>(Td * N * L);
   }
@@ -188,6 +196,7 @@ size_t carve_train(n2nmn_ctx* c, TrainState* t, char* base) {
   t->dxtab_enc = c->big_vocab ? nullptr : k.take<float>(Vt * 4 * L);
   t->dxtab_dec = k.take<float>((V + 1) * 4 * L);
   t->act_count = k.take<int32_t>(8);
+  if (shapes) t->cnn_dfeat_img = k.take<float>(N * HW * D);
   if (c->big_heads) {
     t->hb_en = k.take<float>(N * Mp);
     t->hb_sel = k.take<int32_t>(N);
@@ -208,6 +217,19 @@ size_t carve_train(n2nmn_ctx* c, TrainState* t, char* base) {
     t->qpn_W1T_p = k.take<float>((size_t)round_up((int)Hq, 32) * round_up((int)(2 * L), 64));
   }
   t->dmfind = k.take<float>(N * HW * Mp);
+  if (shapes) {
+    const size_t R = N * HW, C1 = SHAPES_C1;
+    t->cnn_patches = k.take<float>(R * SHAPES_K1);
+    t->cnn_c1 = k.take<float>(R * C1);
+    t->cnn_feat = k.take<float>(R * D);
+    t->cnn_dfeat = k.take<float>(R * D);
+    t->cnn_dz2 = k.take<float>(R * D);
+    t->cnn_dc1 = k.take<float>(R * C1);
+    t->cnn1_p = k.take<float>((size_t)round_up(SHAPES_K1, 32) * round_up(SHAPES_C1, 64));
+    t->cnn2_p = k.take<float>((size_t)round_up(SHAPES_C1, 32) * round_up((int)D, 64));
+    t->find_imgT_p = k.take<float>((size_t)round_up(d.map_dim, 32) * round_up((int)D, 64));
+    t->cnn2T_p = k.take<float>((size_t)round_up((int)D, 32) * round_up(SHAPES_C1, 64));
+  }
   t->dmfsp = k.take<float>(N * HW * Mp);
   t->datts_wv = k.take<float>(Td * T * N);
   t->dE = k.take<float>(T * N * E);
@@ -246,7 +268,7 @@ size_t carve_train(n2nmn_ctx* c, TrainState* t, char* base) {
   t->var_off_dev = k.take<int64_t>(V_COUNT_);
   t->decay_dev = k.take<int32_t>(V_COUNT_);
   t->segs_dev = k.take<ParamSeg>(t->nsegs);
-  t->packs.dev = k.take<PackJob>(16);
+  t->packs.dev = k.take<PackJob>(20);
   return align_up(k.off, 256);
 }
 
@@ -279,10 +301,18 @@ int repack_transposed(n2nmn_ctx* c, hipStream_t s) {
       pb.pk_t(m(V_QPN_W2), Cc, Cc, Hq, t->qpn_W2T_p, round_up(Cc, 32), round_up(Hq, 64));
       pb.pk_t(m(V_QPN_W1), Hq, Hq, 2 * L, t->qpn_W1T_p, round_up(Hq, 32), round_up(2 * L, 64));
     }
+    if (t->cnn1_p) {       // shapes_convnet: both convolutions (forward) and the two W^T of its backward
+      const int D = d.D, M = d.map_dim, C1 = SHAPES_C1;
+      pb.pk(m(V_CNN1_W), C1, SHAPES_K1, C1, t->cnn1_p, round_up(SHAPES_K1, 32), round_up(C1, 64));
+      pb.pk(m(V_CNN2_W), D, C1, D, t->cnn2_p, round_up(C1, 32), round_up(D, 64));
+      pb.pk_t(m(V_FIND_IMG_W), M, M, D, t->find_imgT_p, round_up(M, 32), round_up(D, 64));
+      pb.pk_t(m(V_CNN2_W), D, D, C1, t->cnn2T_p, round_up(D, 32), round_up(C1, 64));
+    }
     const int Ep = round_up(E, 64);
     // B[k][n] = W0[n][k], k < 4L (gate pre-activations), n < E (embedding dims)
     pb.pk_t(m(V_ENC_W0), 4 * L, 4 * L, E, t->enc_W0xT_p, t->KpL4, Ep);
     pb.pk_t(m(V_DEC_W0), 4 * L, 4 * L, E, t->dec_W0xT_p, t->KpL4, Ep);
+    N2_REQUIRE(pb.jobs.size() <= 20, N2NMN_ECAPACITY, "train: transposed pack job table");
     N2_HIP(hipMemcpy(pb.dev, pb.jobs.data(), sizeof(PackJob) * pb.jobs.size(), hipMemcpyHostToDevice));
     pb.uploaded = true;
   }
@@ -605,17 +635,52 @@ int n2nmn_train_forward(n2nmn_ctx* c, const n2nmn_train_io* io, n2nmn_program* p
   sio.T_dec = io->T_dec; sio.use_gt_layout = rl ? 2 : 1; sio.gt_layout = io->gt_layout;
   t->last_N = N; t->last_T = io->T_enc; t->last_Td = io->T_dec;
   const bool vqa = d.variant == N2NMN_VARIANT_VQA;
-  N2_REQUIRE(vqa || !(io->drop_enc0 || io->drop_dec0 || io->drop_qpn_h || io->drop_qpn_fc1),
-             N2NMN_EINVAL, "train_forward: dropout belongs to the models_vqa variant");
+  const bool shapes = d.variant == N2NMN_VARIANT_SHAPES;
+  if (shapes) {
+    N2_REQUIRE(!(io->drop_qpn_h || io->drop_qpn_fc1), N2NMN_EINVAL,
+               "train_forward: models_shapes has no question prior net");
+    N2_REQUIRE(!rl, N2NMN_EINVAL, "train_forward: models_shapes trains with ground-truth layouts only");
+  } else {
+    N2_REQUIRE(vqa || !(io->drop_enc0 || io->drop_dec0 || io->drop_qpn_h || io->drop_qpn_fc1),
+               N2NMN_EINVAL, "train_forward: dropout belongs to the models_vqa variant");
+  }
   sio.drop_enc0 = io->drop_enc0; sio.drop_dec0 = io->drop_dec0;
   c->rec = &t->rec;
   float* scores = io->scores ? io->scores : t->scores;
+  // models_shapes: the module network reads the features shapes_convnet computes from the images
+  const float* feat = shapes ? t->cnn_feat : io->image_feat;
+  if (shapes) {
+    // conv_1 / conv_2 (+ bias, ReLU) as two GEMMs over the im2col rows: side stream, in front of the
+    // hoisted conv_image GEMMs that read their output, beside the encoder
+    hipStream_t sc = t->fork(s);
+    const int R = N * d.H * d.W, C1 = SHAPES_C1, D = d.D;
+    {
+      ProfScope ps(c, F_BWD_MISC, 0.0, 8.0 * R * SHAPES_K1, sc);
+      launch_shapes_im2col(io->image_feat, N, d.H, d.W, t->cnn_patches, sc);
+    }
+    GemmArgs g{};
+    g.A = t->cnn_patches; g.lda = SHAPES_K1; g.M = R; g.K = SHAPES_K1; g.group_size = 1; g.Bp = t->cnn1_p;
+    g.Np = round_up(C1, 64); g.Kp = round_up(SHAPES_K1, 32); g.bias = c->vars[V_CNN1_B].mirror; g.N = C1;
+    g.C = t->cnn_c1; g.ldc = C1; g.n_store = C1; g.relu = 1;
+    {
+      ProfScope ps(c, F_BWD_MISC, 2.0 * R * SHAPES_K1 * C1, 4.0 * ((double)R * (SHAPES_K1 + C1)), sc);
+      launch_gemm_pk(g, sc);
+    }
+    g = GemmArgs{};
+    g.A = t->cnn_c1; g.lda = C1; g.M = R; g.K = C1; g.group_size = 1; g.Bp = t->cnn2_p;
+    g.Np = round_up(D, 64); g.Kp = round_up(C1, 32); g.bias = c->vars[V_CNN2_B].mirror; g.N = D;
+    g.C = t->cnn_feat; g.ldc = D; g.n_store = D; g.relu = 1;
+    {
+      ProfScope ps(c, F_BWD_MISC, 2.0 * R * C1 * D, 4.0 * ((double)R * (C1 + D)), sc);
+      launch_gemm_pk(g, sc);
+    }
+  }
   // the hoisted conv_image GEMMs of the module network need only the image features: they run on
   // the side stream beside the (strictly sequential) encoder
-  rc = run_program(c, p->prog, io->image_feat, c->word_vecs, N, scores, nullptr, nullptr, nullptr,
+  rc = run_program(c, p->prog, feat, c->word_vecs, N, scores, nullptr, nullptr, nullptr,
                    0, 0, s, RP_PREP);
   if (rc == N2NMN_OK)
-    rc = run_program(c, p->prog, io->image_feat, c->word_vecs, N, scores, nullptr, nullptr,
+    rc = run_program(c, p->prog, feat, c->word_vecs, N, scores, nullptr, nullptr,
                      nullptr, 0, 0, t->fork(s), RP_CONV);
   if (rc == N2NMN_OK) rc = encoder_impl(c, &sio, s);
   if (rc == N2NMN_OK) {
@@ -626,9 +691,16 @@ int n2nmn_train_forward(n2nmn_ctx* c, const n2nmn_train_io* io, n2nmn_program* p
     launch_unpack_h(c->fh1, t->rec.dh1s, N, L, d.N, s);
     rc = decoder_impl(c, &sio, s);
   }
+  if (rc == N2NMN_OK && shapes) {
+    // the <eos> latch (models_shapes/nmn3_netgen_att.py:211-222): log_seq_prob and neg_entropy count the
+    // steps up to and including each row's first <eos> (the last layout token)
+    ProfScope ps(c, F_BWD_MISC, 2.0 * io->T_dec * N, 12.0 * io->T_dec * N, s);
+    launch_eos_latch(c->tprobs, c->ent_t, io->gt_layout, io->T_dec, N, d.num_vocab_nmn - 1, t->rec.lsp,
+                     c->negent, s);
+  }
   t->join(s);
   if (rc == N2NMN_OK)
-    rc = run_program(c, p->prog, io->image_feat, c->word_vecs, N, scores, nullptr, nullptr, nullptr,
+    rc = run_program(c, p->prog, feat, c->word_vecs, N, scores, nullptr, nullptr, nullptr,
                      0, 0, s, RP_REST);
   c->rec = nullptr;
   if (rc != N2NMN_OK) return rc;
@@ -681,6 +753,8 @@ int n2nmn_train_backward(n2nmn_ctx* c, const n2nmn_train_io* io, n2nmn_program* 
   const int Ep = round_up(E, 64);
   auto G = [&](int var) { return gptr(c, io, var); };
   auto mir = [&](int var) { return (const float*)c->vars[var].mirror; };
+  const bool shapes = d.variant == N2NMN_VARIANT_SHAPES;
+  const float* feat = shapes ? t->cnn_feat : io->image_feat;     // what the module network read
 
   if (phase == 0) {
     // ------------------------------- module network ---------------------------------------
@@ -735,7 +809,7 @@ int n2nmn_train_backward(n2nmn_ctx* c, const n2nmn_train_io* io, n2nmn_program* 
       ModuleWeights w = module_weights(c);
       ModuleBuffers b{};
       b.nodes = c->dev_nodes; b.tab = c->dev_tab; b.arena = c->arena; b.tmap = c->tmap;
-      b.pfc = c->pfc; b.mfind = c->mfind; b.mfsp = c->mfsp; b.feat = io->image_feat;
+      b.pfc = c->pfc; b.mfind = c->mfind; b.mfsp = c->mfsp; b.feat = feat;
       b.word_vecs = c->word_vecs; b.scores = nullptr; b.N_full = N; b.H = d.H; b.W = d.W; b.D = D;
       b.M = M; b.Mp = Mp; b.wl_cap = 0; b.E = E; b.C = C; b.HWp = c->HWp; b.ksize = d.kernel_size;
       b.pooled = t->rec.pooled;
@@ -830,9 +904,33 @@ int n2nmn_train_backward(n2nmn_ctx* c, const n2nmn_train_io* io, n2nmn_program* 
               }
             } else {
               const bool fsp = l.kind == LK_CONV_FSP;
-              gemm_tn(c, sd, io->image_feat, D, D, fsp ? t->dmfsp : t->dmfind, Mp, M, l.count * HW,
+              gemm_tn(c, sd, feat, D, D, fsp ? t->dmfsp : t->dmfind, Mp, M, l.count * HW,
                       G(fsp ? V_FSP_IMG_W : V_FIND_IMG_W), M, c->dev_tab + l.offset, HW, nullptr, 0,
                       nullptr, nullptr, G(fsp ? V_FSP_IMG_B : V_FIND_IMG_B));
+              if (shapes && !fsp) {
+                // shapes_convnet backward over the image slots of the Find nodes (slot q = image
+                // tab[q]; the Find backward has summed the slot's d conv_image map over every Find
+                // node of that image).  Leaves of the backward graph: side stream.
+                const int32_t* tab = c->dev_tab + l.offset;
+                const int R = l.count * HW, C1 = SHAPES_C1;
+                // d image_feat = dM . W_img^T
+                gemm_nt(c, sd, t->dmfind, Mp, R, M, t->find_imgT_p, round_up(D, 64), round_up(M, 32), D,
+                        t->cnn_dfeat, D, false);
+                {
+                  ProfScope ps(c, F_BWD_MISC, (double)R * D, 4.0 * 4 * R * D, sd);
+                  launch_relu_bwd_rows(t->cnn_dfeat, t->cnn_feat, tab, HW, R, D, t->cnn_dz2, t->cnn_dfeat_img, sd);
+                }
+                gemm_tn(c, sd, t->cnn_c1, C1, C1, t->cnn_dz2, D, D, R, G(V_CNN2_W), D, tab, HW, nullptr, 0,
+                        nullptr, nullptr, G(V_CNN2_B));
+                gemm_nt(c, sd, t->cnn_dz2, D, R, D, t->cnn2T_p, round_up(C1, 64), round_up(D, 32), C1,
+                        t->cnn_dc1, C1, false);
+                {
+                  ProfScope ps(c, F_BWD_MISC, (double)R * C1, 4.0 * 3 * R * C1, sd);
+                  launch_relu_bwd_rows(t->cnn_dc1, t->cnn_c1, tab, HW, R, C1, t->cnn_dc1, nullptr, sd);
+                }
+                gemm_tn(c, sd, t->cnn_patches, SHAPES_K1, SHAPES_K1, t->cnn_dc1, C1, C1, R, G(V_CNN1_W), C1,
+                        tab, HW, nullptr, 0, nullptr, nullptr, G(V_CNN1_B));
+              }
             }
             break;
           }
@@ -895,6 +993,7 @@ int n2nmn_train_backward(n2nmn_ctx* c, const n2nmn_train_io* io, n2nmn_program* 
     a.eout = c->enc_out; a.atts = c->atts; a.datts_wv = t->datts_wv; a.seq_len = io->seq_length;
     a.v = mir(V_ATT_V); a.Wy = mir(V_TOK_W); a.T = T; a.N = N; a.L = L; a.V = V; a.Td = Td;
     a.inv_n = 1.0f / (float)N;
+    if (shapes) { a.latch = 1; a.eos = V - 1; }
     if (io->objective == N2NMN_OBJ_POLICY_GRADIENT) {
       a.coef = t->rl_coef; a.valid_bits = t->rec.valid_bits;
       a.ent_coef = io->lambda_entropy / (float)N;
@@ -1170,6 +1269,8 @@ int64_t n2nmn_train_debug_tensor(n2nmn_ctx* c, const char* name, float* out, int
   else if (k == "d_scores") { src = t->dscores; n = N * d.num_choices; }
   else if (k == "d_dec_out") { src = t->dout; n = Td * N * L; }
   else if (k == "d_state") { src = t->dH0; n = 4 * (int64_t)d.N * L; }
+  else if (k == "token_scores") { src = t->rec.tscores; n = Td * N * d.num_vocab_nmn; }
+  else if (k == "d_image_feat" && t->cnn_dfeat_img) { src = t->cnn_dfeat_img; n = N * d.H * d.W * d.D; }
   else {
     set_last_error("train_debug_tensor: unknown tensor '" + k + "'");
     return N2NMN_EKEY;

@@ -95,6 +95,7 @@ enum VarId {
   V_SP_TXT_W, V_SP_TXT_B, V_SP_ATT0_W, V_SP_ATT0_B, V_SP_ATT1_W, V_SP_ATT1_B, V_SP_E_W, V_SP_E_B,
   V_DE_TXT_W, V_DE_TXT_B, V_DE_ATT_W, V_DE_ATT_B, V_DE_E_W, V_DE_E_B,
   V_QPN_W1, V_QPN_B1, V_QPN_W2, V_QPN_B2,      // models_vqa/question_prior_net.py (VQA variant only)
+  V_CNN1_W, V_CNN1_B, V_CNN2_W, V_CNN2_B,      // models_shapes/shapes_convnet.py (SHAPES variant only)
   V_COUNT_
 };
 

@@ -549,6 +549,9 @@ struct DecBwdArgs {
   // d loss / d log p(chosen token) per question (nullptr: -1/N, behavioural cloning), validity
   // bits of the forward (nullptr: all valid), weight of d neg_entropy (lambda_entropy / N)
   const float* coef; const int32_t* valid_bits; float ent_coef;
+  // models_shapes' <eos> latch (nmn3_netgen_att.py:211-222): latch != 0 -> steps behind the row's first
+  // gt token == eos have token probability 1 and entropy 0, hence a zero token-logit gradient
+  int latch, eos;
   float* dsc;              // [Td][N][16] d token logits (zero padded)
   float* dout;             // [Td][N][L] direct part of d(top-layer h)
   float* dctx;             // [Td][N][L]
@@ -590,6 +593,22 @@ void launch_qpn_dh_add(const float* dh, const float* mh, float* dH0, float* dH1,
 void launch_loss_total(float* losses, float wd, float lambda_entropy, hipStream_t s);
 // zero up to 6 byte ranges (4-byte aligned starts and sizes) in ONE launch: a memset node costs ~5 us
 // on the stream whatever its size, and the backward pass starts with four of them
+// models_shapes/shapes_convnet.py:8-17: conv_1 = 10x10 stride-10 VALID over 3 channels -> 64, conv_2 = 1x1
+constexpr int SHAPES_PATCH = 10;
+constexpr int SHAPES_C1 = 64;
+constexpr int SHAPES_K1 = SHAPES_PATCH * SHAPES_PATCH * 3;
+// patches[(n*H + i)*W + j][(a*10 + b)*3 + ch] = img[n][10i + a][10j + b][ch]   (im2col of conv_1: a permutation)
+void launch_shapes_im2col(const float* img, int N, int H, int W, float* patches, hipStream_t s);
+// ReLU backward over gathered rows: row r of `dy` belongs to source row src(r) = tab[r / gs] * gs + r % gs
+// of `y` (the ReLU's output):  dx[r] = y[src] > 0 ? dy[r] : 0  (dx may be dy); scatter != nullptr: also
+// scatter[src] = dy[r]   (rows x ncols, all row-major with ld = ncols)
+void launch_relu_bwd_rows(const float* dy, const float* y, const int32_t* tab, int gs, int rows, int ncols,
+                          float* dx, float* scatter, hipStream_t s);
+// the <eos> latch of models_shapes on the forward's per-step outputs: log_seq_prob[n] = sum of log tprobs and
+// neg_entropy[n] = sum of ent_t over the steps up to and including the first gt[t][n] == eos
+void launch_eos_latch(const float* tprobs, const float* ent_t, const int32_t* gt, int Td, int N, int eos,
+                      float* log_seq_prob, float* neg_entropy, hipStream_t s);
+
 struct ZeroRanges { void* ptr[6]; size_t bytes[6]; int n; };
 void launch_zero_ranges(const ZeroRanges& z, hipStream_t s);
 

@@ -628,7 +628,11 @@ __global__ __launch_bounds__(256) void dec_bwd_a_kernel(DecBwdArgs a) {
     const float pv = ex / den;
     const float coef = a.coef ? a.coef[n] : -a.inv_n;
     float d = valid ? coef * ((lane == a.gt[tn] ? 1.f : 0.f) - pv) : 0.f;
-    if (a.ent_coef != 0.f) {
+    bool latched = false;               // models_shapes: an <eos> in an earlier step of this row
+    if (a.latch)
+      for (int u = 0; u < t; ++u) latched = latched || a.gt[(size_t)u * N + n] == a.eos;
+    if (latched) d = 0.f;
+    if (a.ent_coef != 0.f && !latched) {
       const float gv = valid ? (pv >= 1e-5f ? logf(pv) + 1.f : logf(1e-5f)) : 0.f;
       const float pg = wave_sum(pv * gv);
       d += valid ? a.ent_coef * pv * (gv - pg) : 0.f;
@@ -890,6 +894,53 @@ __global__ __launch_bounds__(256) void loss_kernel(const float* __restrict__ sco
     losses[0] = (part[0][0] + part[1][0] + part[2][0] + part[3][0]) / (float)N;
     losses[1] = (part[0][1] + part[1][1] + part[2][1] + part[3][1]) / (float)N;
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// models_shapes: im2col of shapes_convnet's conv_1, the ReLU backward of its two layers over the
+// image-slot rows of the Find backward, and the <eos> latch of the teacher-forced log_seq_prob.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void shapes_im2col_kernel(const float* __restrict__ img, int H, int W,
+                                                            size_t total, float* __restrict__ patches) {
+  // one thread per output element; the 30 floats of a kernel row (b, ch) are contiguous on both sides
+  const int Wi = W * SHAPES_PATCH;
+  for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+    const size_t r = e / SHAPES_K1;
+    const int k = (int)(e - r * SHAPES_K1);
+    const int a = k / (SHAPES_PATCH * 3), bc = k - a * SHAPES_PATCH * 3;
+    const size_t n = r / ((size_t)H * W);
+    const int ij = (int)(r - n * H * W), i = ij / W, j = ij - i * W;
+    patches[e] = img[((n * H * SHAPES_PATCH + (size_t)i * SHAPES_PATCH + a) * Wi + (size_t)j * SHAPES_PATCH) * 3 + bc];
+  }
+}
+
+__global__ __launch_bounds__(256) void relu_bwd_rows_kernel(const float* dy, const float* __restrict__ y,
+                                                            const int32_t* __restrict__ tab, int gs, size_t total,
+                                                            int ncols, float* dx, float* __restrict__ scatter) {
+  for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+    const size_t r = e / ncols;
+    const int col = (int)(e - r * ncols);
+    const size_t src = (size_t)tab[r / gs] * gs + r % gs;
+    const float g = dy[e];
+    if (scatter) scatter[src * ncols + col] = g;
+    dx[e] = y[src * ncols + col] > 0.f ? g : 0.f;
+  }
+}
+
+__global__ __launch_bounds__(256) void eos_latch_kernel(const float* __restrict__ tprobs,
+                                                        const float* __restrict__ ent_t,
+                                                        const int32_t* __restrict__ gt, int Td, int N, int eos,
+                                                        float* __restrict__ lsp, float* __restrict__ negent) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  float s = 0.f, e = 0.f;
+  for (int t = 0; t < Td; ++t) {      // same order of additions as word_vecs_kernel
+    s += logf(tprobs[(size_t)t * N + n]);
+    e += ent_t[(size_t)t * N + n];
+    if (gt[(size_t)t * N + n] == eos) break;
+  }
+  lsp[n] = s;
+  if (negent) negent[n] = e;
 }
 
 // Dropout multipliers from a counter-based generator: element i of the stream (seed, offset + i)
@@ -1234,6 +1285,24 @@ void launch_embed_scatter(const float* src, const int32_t* idx, const int32_t* r
 }
 
 static int ew_blocks(size_t n) { return (int)std::min<size_t>((n + 255) / 256, 1024); }
+void launch_shapes_im2col(const float* img, int N, int H, int W, float* patches, hipStream_t s) {
+  const size_t total = (size_t)N * H * W * SHAPES_K1;
+  if (total == 0) return;
+  hipLaunchKernelGGL(shapes_im2col_kernel, dim3(ew_blocks(total)), dim3(256), 0, s, img, H, W, total, patches);
+}
+void launch_relu_bwd_rows(const float* dy, const float* y, const int32_t* tab, int gs, int rows, int ncols,
+                          float* dx, float* scatter, hipStream_t s) {
+  const size_t total = (size_t)rows * ncols;
+  if (total == 0) return;
+  hipLaunchKernelGGL(relu_bwd_rows_kernel, dim3(ew_blocks(total)), dim3(256), 0, s, dy, y, tab, gs, total, ncols,
+                     dx, scatter);
+}
+void launch_eos_latch(const float* tprobs, const float* ent_t, const int32_t* gt, int Td, int N, int eos,
+                      float* log_seq_prob, float* neg_entropy, hipStream_t s) {
+  if (N <= 0) return;
+  hipLaunchKernelGGL(eos_latch_kernel, dim3((N + 255) / 256), dim3(256), 0, s, tprobs, ent_t, gt, Td, N, eos,
+                     log_seq_prob, neg_entropy);
+}
 void launch_dropout_mult(float* out, size_t n, float keep_prob, unsigned long long seed,
                          unsigned long long offset, hipStream_t s) {
   hipLaunchKernelGGL(dropout_mult_kernel, dim3(ew_blocks(n)), dim3(256), 0, s, out, n, keep_prob, seed,

@@ -23,6 +23,11 @@ What models_shapes is made of, and where it runs here:
     Answer = fc([min, mean, max]) = the CLEVR operators' kernels (Answer has ExistModule's arithmetic).
 token_probs / neg_entropy / log_seq_prob of models_shapes follow the latch too (probability 1, entropy 0 behind
 the <eos>) and are not offered by this inference face.
+
+Training (exp_shapes/train_shapes_gt_layout.py:143-163) is `ShapesTrainer`: an engine of the model variant
+N2NMN_VARIANT_SHAPES (include/n2nmn.h), whose training step runs shapes_convnet forward and backward, the <eos>
+latch of the teacher-forced loss and layer-0 LSTM dropout on the GPU.  A trained model is evaluated through
+this face: NMN3ModelAtt.load_weights(trainer.get_weights()).
 """
 from __future__ import annotations
 
@@ -31,8 +36,10 @@ import numpy as np
 from .engine import Engine, _torch
 from .nmn3_assembler import Assembler as _Assembler
 from .nmn3_model import Compiler
+from . import _lib
 from .runtime import Fetch, register_model, resolve, to_numpy
 from .spec import Dims, variable_shapes
+from .train import Trainer
 
 SHAPES_MODULE_NAMES = ('_Find', '_Transform', '_And', '_Answer', '<eos>')   # exp_shapes/data/vocabulary_layout.txt
 # module -> C-ABI operator; _Answer = fc([min, mean, max]) is ExistModule's arithmetic (nmn3_modules.py:122-144)
@@ -178,4 +185,166 @@ class NMN3ModelAtt:
         return to_numpy(handle.results['scores'])
 
 
-__all__ = ['Assembler', 'NMN3ModelAtt', 'SHAPES_MODULE_NAMES']
+# ---------------------------------------------------------------------------------------------------------
+# training: the N2NMN_VARIANT_SHAPES engine
+VARIANT_SHAPES = 2                                       # include/n2nmn.h N2NMN_VARIANT_SHAPES
+_ENGINE_MOD = _MOD + 'module_variables/'
+# engine module scope -> the reference's (nmn3_model.py:60-80: td.ScopedLayer opens <X>Module twice)
+_MODULE_SCOPES = {'FindModule': 'FindModule', 'TransformModule': 'TransformModule', 'ExistModule': 'AnswerModule'}
+
+
+def reference_name(engine_name: str) -> str:
+    """engine variable name -> models_shapes variable name (module_variables/<X>Module/... ->
+    layout_execution/<Y>/<Y>/..., ExistModule -> AnswerModule); other names are shared"""
+    if not engine_name.startswith(_ENGINE_MOD):
+        return engine_name
+    scope, rest = engine_name[len(_ENGINE_MOD):].split('/', 1)
+    ref = _MODULE_SCOPES[scope]
+    return _MOD + ref + '/' + ref + '/' + rest
+
+
+def shapes_dims(num_vocab_txt: int, N: int = 256, T_encoder: int = 15, T_decoder: int = 11, lstm_dim: int = 256,
+                embed_dim: int = 300, map_dim: int = 500, feat_dim: int = 64, num_choices: int = 2,
+                H_im: int = 30, W_im: int = 30) -> Dims:
+    """dimensions of the models_shapes training engine (defaults: exp_shapes/train_shapes_gt_layout.py:23-37)"""
+    if H_im % 10 or W_im % 10:
+        raise ValueError('image size must be a multiple of the 10x10 stride-10 kernel')
+    return Dims(H=H_im // 10, W=W_im // 10, D=feat_dim, map_dim=map_dim, embed_dim_txt=embed_dim,
+                embed_dim_nmn=embed_dim, lstm_dim=lstm_dim, num_layers=2, num_vocab_txt=num_vocab_txt,
+                num_vocab_nmn=len(SHAPES_MODULE_NAMES), num_choices=num_choices, T_encoder=T_encoder,
+                T_decoder=T_decoder, N=N, kernel_size=3, variant=VARIANT_SHAPES)
+
+
+def shapes_engine_variable_shapes(d: Dims) -> dict:
+    """engine name -> shape of the N2NMN_VARIANT_SHAPES variable table, in its order (host-side statement of
+    csrc/capi.cpp build_vars for this variant: the seq2seq, the three modules models_shapes has, the convnet)"""
+    full = variable_shapes(d)
+    keep = ('FindModule/', 'TransformModule/', 'ExistModule/')
+    out = {k: v for k, v in full.items()
+           if not k.startswith(_ENGINE_MOD) or k[len(_ENGINE_MOD):].startswith(keep)}
+    out[_CNN + 'conv_1/weights'] = (10, 10, 3, 64)
+    out[_CNN + 'conv_1/biases'] = (64,)
+    out[_CNN + 'conv_2/weights'] = (1, 1, 64, d.D)
+    out[_CNN + 'conv_2/biases'] = (d.D,)
+    return out
+
+
+def l2_variables(names) -> set:
+    """models_shapes/nmn3_model.py:104-108: the trainable variables under neural_module_network whose name ends
+    in 'weights' (the set weight_decay * l2_reg covers; the engine applies the same rule to its own names)"""
+    return {k for k in names if 'neural_module_network' in k and k.endswith('weights')}
+
+
+def shapes_engine(num_vocab_txt: int, device: int = 0, **kw) -> Engine:
+    """an Engine of the SHAPES variant, decoding without a validity automaton (all-valid tables)"""
+    d = shapes_dims(num_vocab_txt, **kw)
+    asm = _Assembler(list(SHAPES_MODULE_NAMES), op_code=SHAPES_OP_CODE, input_num=SHAPES_INPUT_NUM,
+                     output_type=SHAPES_OUTPUT_TYPE)
+    e = Engine(d, asm, device)
+    V = d.num_vocab_nmn
+    e.set_validity_tables(np.zeros((V, 3), np.int32), np.zeros((3, V, 4), np.int32), np.zeros((V, 4), np.int32))
+    return e
+
+
+class ShapesTrainer(Trainer):
+    """One iteration of exp_shapes/train_shapes_gt_layout.py:143-163 on the GPU: shapes_convnet + the layout
+    generator (teacher-forced, <eos> latch, encoder / decoder dropout on LSTM layer 0, keep_prob 0.5) + the
+    modules; total = mean(CE) + mean(-log_seq_prob) + weight_decay * l2_reg; per-tensor clip_by_norm(10);
+    Adam.  Every gradient, the convnet's included, is computed on the GPU.
+
+    step(batch, gt_layout, dropout=None): batch holds image_batch [N, H_im, W_im, 3] (mean-subtracted),
+    input_seq_batch [T, N], seq_length_batch [N], answer_label_batch [N].  dropout: None = masks drawn with
+    n2nmn_dropout_multipliers from the trainer's seed stream (if the trainer has dropout on); False = no
+    dropout for this step; or a dict {'enc0': [T, N, lstm_dim], 'dec0': [T_dec, N, lstm_dim]} of {0, 1} keep
+    masks.  gradients() / get_weights() / load_weights() use the reference's models_shapes names."""
+
+    def __init__(self, engine: Engine, weight_decay: float = 5e-4, lr: float = 1e-3,
+                 max_grad_l2_norm: float = 10.0, encoder_dropout: bool = True, decoder_dropout: bool = True,
+                 keep_prob: float = 0.5, seed: int = 0, dist=None, rccl=None):
+        if engine.dims.variant != VARIANT_SHAPES:
+            raise ValueError('ShapesTrainer needs an engine of the SHAPES variant (shapes_engine())')
+        super().__init__(engine, weight_decay=weight_decay, lr=lr, max_grad_l2_norm=max_grad_l2_norm,
+                         dist=dist, rccl=rccl)
+        self.dropout = dict(enc0=bool(encoder_dropout), dec0=bool(decoder_dropout))
+        self.keep_prob = float(keep_prob)
+        self.seed = int(seed)
+        self._drawn = 0
+        self._step_dropout = None
+        self._mult = None
+        self.ref_layout = {reference_name(k): v for k, v in self.layout.items()}
+
+    def _multipliers(self, T, N, Td, dropout):
+        torch = _torch()
+        dev, L = self.engine.device, self.engine.dims.lstm_dim
+        shapes = dict(enc0=(T, N, L), dec0=(Td, N, L))
+        out = {}
+        if dropout is False:
+            return out
+        for key, on in self.dropout.items():
+            if isinstance(dropout, dict):
+                if key not in dropout or dropout[key] is None:
+                    continue
+                keep = torch.as_tensor(np.asarray(dropout[key], np.float32), device=dev)
+                if tuple(keep.shape) != shapes[key]:
+                    raise ValueError('dropout mask %s: shape %s, expected %s' % (key, tuple(keep.shape), shapes[key]))
+                m = keep / self.keep_prob
+            elif on:
+                m = torch.empty(shapes[key], dtype=torch.float32, device=dev)
+                _lib.check(self._lib.n2nmn_dropout_multipliers(m.data_ptr(), m.numel(), self.keep_prob, self.seed,
+                                                               self._drawn, self.engine.stream()))
+                self._drawn += m.numel()
+            else:
+                continue
+            out[key] = m.contiguous()
+        return out
+
+    def _io(self, batch, gt_layout, objective: int = 0):
+        b = dict(batch)
+        b['image_feat_batch'] = batch['image_batch']
+        io, packed, validity = super()._io(b, gt_layout, objective)
+        T, N = io.T_enc, io.N
+        self._mult = self._multipliers(T, N, io.T_dec, self._step_dropout)
+        if 'enc0' in self._mult:
+            io.drop_enc0 = self._mult['enc0'].data_ptr()
+        if 'dec0' in self._mult:
+            io.drop_dec0 = self._mult['dec0'].data_ptr()
+        return io, packed, validity
+
+    def step(self, batch, gt_layout, dropout=None):
+        """one iteration; returns the losses (device tensor: avg_sample_loss, seq_likelihood_loss, l2_reg,
+        total_loss, ...)"""
+        self._step_dropout = dropout
+        try:
+            return super().step(batch, gt_layout)
+        finally:
+            self._step_dropout = None
+
+    def forward_backward(self, batch, gt_layout, reduce: bool = True, objective: int = 0, dropout=None) -> float:
+        if objective != 0:
+            raise NotImplementedError('models_shapes trains with ground-truth layouts (behavioural cloning) here')
+        if dropout is not None:
+            self._step_dropout = dropout
+        return super().forward_backward(batch, gt_layout, reduce=reduce, objective=0)
+
+    def step_rl(self, *a, **k):
+        raise NotImplementedError('the policy-gradient objective of models_shapes is not part of this trainer')
+
+    # -- reference names ---------------------------------------------------------------------------------
+    def gradients(self):
+        return {reference_name(k): v for k, v in super().gradients().items()}
+
+    def get_weights(self):
+        return {reference_name(k): v for k, v in super().get_weights().items()}
+
+    def load_weights(self, weights):
+        """models_shapes-named variables (oracle/n2nmn_oracle_shapes.variable_shapes lists them)"""
+        inv = {reference_name(k): k for k in self.layout}
+        missing = sorted(set(inv) - set(weights))
+        extra = sorted(set(weights) - set(inv))
+        if missing or extra:
+            raise KeyError('models_shapes variables: missing %s, unknown %s' % (missing[:4], extra[:4]))
+        self.engine.load_weights({inv[k]: v for k, v in weights.items()})
+
+
+__all__ = ['Assembler', 'NMN3ModelAtt', 'SHAPES_MODULE_NAMES', 'ShapesTrainer', 'shapes_engine', 'shapes_dims',
+           'reference_name', 'shapes_engine_variable_shapes', 'l2_variables']
