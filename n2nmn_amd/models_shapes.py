@@ -36,8 +36,7 @@ import numpy as np
 from .engine import Engine, _torch
 from .nmn3_assembler import Assembler as _Assembler
 from .nmn3_model import Compiler
-from . import _lib
-from .runtime import Fetch, register_model, resolve, to_numpy
+from .runtime import Fetch, Phase1Inputs, register_model, resolve, to_numpy
 from .spec import Dims, variable_shapes
 from .train import Trainer
 
@@ -101,8 +100,7 @@ class NMN3ModelAtt:
         self.T_decoder = T_decoder
         self.hidden_dim = hidden_dim
         self.image_batch = image_batch
-        self._inputs = dict(input_seq=text_seq_batch, seq_len=seq_length_batch, use_gt_layout=use_gt_layout,
-                            gt_layout=gt_layout_batch)
+        self.phase1_inputs = Phase1Inputs(text_seq_batch, seq_length_batch, use_gt_layout, gt_layout_batch)
         self._cnn = None
         for name in ('predicted_tokens', 'word_vecs', 'atts'):
             setattr(self, name, Fetch(self, name, 1))
@@ -154,12 +152,7 @@ class NMN3ModelAtt:
 
     def run_phase1(self, feeds=None):
         feeds = feeds or {}
-        seq = resolve(self._inputs['input_seq'], feeds)
-        lens = resolve(self._inputs['seq_len'], feeds)
-        use_gt = self._inputs['use_gt_layout']
-        use_gt = bool(resolve(use_gt, feeds)) if use_gt is not None else False
-        gt = self._inputs['gt_layout']
-        gt = resolve(gt, feeds) if (gt is not None and use_gt) else None
+        seq, lens, use_gt, gt = self.phase1_inputs.resolve(feeds)
         out = dict(self.engine.seq2seq(seq, lens, self.T_decoder, use_gt, gt))
         # the <eos> latch of models_shapes/nmn3_netgen_att.py:215-222: behind the first <eos> every token is <eos>
         tok = to_numpy(out['predicted_tokens']).copy()
@@ -253,10 +246,10 @@ class ShapesTrainer(Trainer):
     Adam.  Every gradient, the convnet's included, is computed on the GPU.
 
     step(batch, gt_layout, dropout=None): batch holds image_batch [N, H_im, W_im, 3] (mean-subtracted),
-    input_seq_batch [T, N], seq_length_batch [N], answer_label_batch [N].  dropout: None = masks drawn with
-    n2nmn_dropout_multipliers from the trainer's seed stream (if the trainer has dropout on); False = no
-    dropout for this step; or a dict {'enc0': [T, N, lstm_dim], 'dec0': [T_dec, N, lstm_dim]} of {0, 1} keep
-    masks.  gradients() / get_weights() / load_weights() use the reference's models_shapes names."""
+    input_seq_batch [T, N], seq_length_batch [N], answer_label_batch [N].  dropout: None = multipliers drawn
+    from the trainer's dropout_stream (seed) for the switched-on sites; False = no dropout for this step; or a
+    dict {'enc0': [T, N, lstm_dim], 'dec0': [T_dec, N, lstm_dim]} of {0, 1} keep masks.  gradients() /
+    get_weights() / load_weights() use the reference's models_shapes names."""
 
     def __init__(self, engine: Engine, weight_decay: float = 5e-4, lr: float = 1e-3,
                  max_grad_l2_norm: float = 10.0, encoder_dropout: bool = True, decoder_dropout: bool = True,
@@ -266,65 +259,17 @@ class ShapesTrainer(Trainer):
         super().__init__(engine, weight_decay=weight_decay, lr=lr, max_grad_l2_norm=max_grad_l2_norm,
                          dist=dist, rccl=rccl)
         self.dropout = dict(enc0=bool(encoder_dropout), dec0=bool(decoder_dropout))
-        self.keep_prob = float(keep_prob)
-        self.seed = int(seed)
-        self._drawn = 0
-        self._step_dropout = None
-        self._mult = None
+        self.dropout_stream.keep_prob = float(keep_prob)
+        self.dropout_stream.seed = int(seed)
         self.ref_layout = {reference_name(k): v for k, v in self.layout.items()}
 
-    def _multipliers(self, T, N, Td, dropout):
-        torch = _torch()
-        dev, L = self.engine.device, self.engine.dims.lstm_dim
-        shapes = dict(enc0=(T, N, L), dec0=(Td, N, L))
-        out = {}
-        if dropout is False:
-            return out
-        for key, on in self.dropout.items():
-            if isinstance(dropout, dict):
-                if key not in dropout or dropout[key] is None:
-                    continue
-                keep = torch.as_tensor(np.asarray(dropout[key], np.float32), device=dev)
-                if tuple(keep.shape) != shapes[key]:
-                    raise ValueError('dropout mask %s: shape %s, expected %s' % (key, tuple(keep.shape), shapes[key]))
-                m = keep / self.keep_prob
-            elif on:
-                m = torch.empty(shapes[key], dtype=torch.float32, device=dev)
-                _lib.check(self._lib.n2nmn_dropout_multipliers(m.data_ptr(), m.numel(), self.keep_prob, self.seed,
-                                                               self._drawn, self.engine.stream()))
-                self._drawn += m.numel()
-            else:
-                continue
-            out[key] = m.contiguous()
-        return out
-
-    def _io(self, batch, gt_layout, objective: int = 0):
-        b = dict(batch)
-        b['image_feat_batch'] = batch['image_batch']
-        io, packed, validity = super()._io(b, gt_layout, objective)
-        T, N = io.T_enc, io.N
-        self._mult = self._multipliers(T, N, io.T_dec, self._step_dropout)
-        if 'enc0' in self._mult:
-            io.drop_enc0 = self._mult['enc0'].data_ptr()
-        if 'dec0' in self._mult:
-            io.drop_dec0 = self._mult['dec0'].data_ptr()
-        return io, packed, validity
-
-    def step(self, batch, gt_layout, dropout=None):
-        """one iteration; returns the losses (device tensor: avg_sample_loss, seq_likelihood_loss, l2_reg,
-        total_loss, ...)"""
-        self._step_dropout = dropout
-        try:
-            return super().step(batch, gt_layout)
-        finally:
-            self._step_dropout = None
+    def _io(self, batch, *args):
+        return super()._io(dict(batch, image_feat_batch=batch['image_batch']), *args)
 
     def forward_backward(self, batch, gt_layout, reduce: bool = True, objective: int = 0, dropout=None) -> float:
         if objective != 0:
             raise NotImplementedError('models_shapes trains with ground-truth layouts (behavioural cloning) here')
-        if dropout is not None:
-            self._step_dropout = dropout
-        return super().forward_backward(batch, gt_layout, reduce=reduce, objective=0)
+        return super().forward_backward(batch, gt_layout, reduce=reduce, dropout=dropout)
 
     def step_rl(self, *a, **k):
         raise NotImplementedError('the policy-gradient objective of models_shapes is not part of this trainer')

@@ -32,7 +32,7 @@ from .data_reader import DataReader as _DataReader
 from .nmn3_assembler import Assembler as _Assembler
 from .nmn3_model import Compiler
 from .nmn3_netgen_att import PHASE1_OUTPUTS
-from .runtime import Fetch, register_model, resolve, to_numpy
+from .runtime import Fetch, Phase1Inputs, SamplingUniforms, register_model, resolve, to_numpy
 from .vqa import VQA_MODULE_NAMES, VQA_OP_CODE, VQADims, VQAEngine
 
 
@@ -68,8 +68,9 @@ class NMN3Model:
         # fetch outside a training handle runs without dropout (what the eval scripts build)
         self.dropout = dict(enc0=bool(encoder_dropout), dec0=bool(decoder_dropout), qpn=bool(qpn_dropout))
         self.decoder_sampling = bool(decoder_sampling)
-        self.dropout_seed, self.sample_seed = 0, 0
-        self._drop_gen = self._sample_gen = None
+        self.dropout_seed = 0
+        self._drop_gen = None
+        self.sampling = SamplingUniforms(0)
         self.dropout_masks = None            # tests: {'enc0','dec0','qpn_h','qpn_fc1'} keep masks for the NEXT handle
         self.last_masks = None
         if list(assembler.module_names) != list(VQA_MODULE_NAMES):
@@ -103,8 +104,7 @@ class NMN3Model:
         self.qpn_dropout = qpn_dropout
         self.reduce_visfeat_dim = reduce_visfeat_dim
         self.image_feat_grid = image_feat_grid
-        self._inputs = dict(input_seq=text_seq_batch, seq_len=seq_length_batch, use_gt_layout=use_gt_layout,
-                            gt_layout=gt_layout_batch)
+        self.phase1_inputs = Phase1Inputs(text_seq_batch, seq_length_batch, use_gt_layout, gt_layout_batch)
         for name in PHASE1_OUTPUTS:
             setattr(self, name, Fetch(self, name, 1))
         self.compiler = Compiler(assembler)
@@ -146,59 +146,32 @@ class NMN3Model:
                         max_grad_l2_norm=float(op.clip_norm) if op.clip_norm is not None else 0.0)
         return tr
 
-    def _draw_masks(self, T, N):
-        """{0, 1} keep masks of one handle, reference-shaped (VQATrainer._multipliers pads them)"""
-        d = self.vqa.dims
+    def _draw_masks(self, tr, T, N):
+        """{0, 1} keep masks of one handle, reference-shaped, for the trainer's dropout sites"""
         if self.dropout_masks is not None:
             masks, self.dropout_masks = self.dropout_masks, None
             return masks
         if self._drop_gen is None:
             self._drop_gen = np.random.default_rng(self.dropout_seed)
         g = self._drop_gen
-        shapes = dict(enc0=(T, N, d.lstm_dim), dec0=(self.T_decoder, N, d.lstm_dim),
-                      qpn_h=(N, d.num_layers * d.lstm_dim), qpn_fc1=(N, d.qpn_hidden))
-        on = dict(enc0=self.dropout['enc0'], dec0=self.dropout['dec0'], qpn_h=self.dropout['qpn'] and self.use_qpn,
-                  qpn_fc1=self.dropout['qpn'] and self.use_qpn and d.qpn_hidden > 0)
-        return {k: (g.random(shapes[k]) < 0.5).astype(np.float32) for k in shapes if on[k]}
+        return {k: (g.random(s) < 0.5).astype(np.float32) for k, s in tr.dropout_shapes(T, N, self.T_decoder).items()}
 
     def run_phase1_training(self, handle):
-        """phase 1 of a handle that will fetch `train_step`: this handle's dropout masks are drawn here, the
-        decoder runs (and samples) under them, and the trainer is told to differentiate under the same ones"""
-        feeds = handle.feeds
-        step = handle.train_step()
-        tr = step.ensure_trainer()
-        seq = resolve(self._inputs['input_seq'], feeds)
-        lens = resolve(self._inputs['seq_len'], feeds)
+        """phase 1 of a handle that will fetch `train_step`: this handle's dropout masks are drawn here and kept
+        on the handle; the decoder runs (and samples) under them, and the step differentiates under the same ones"""
+        tr = handle.train_step().ensure_trainer()
+        seq, lens, use_gt, gt = self.phase1_inputs.resolve(handle.feeds)
         T, N = np.asarray(to_numpy(seq)).shape
-        masks = self._draw_masks(T, N)
-        self.last_masks = masks
-        tr.masks = masks
-        mult = tr._multipliers(T, N, self.T_decoder)
-        tr.masks = None
-        tr._reuse = mult
-        use_gt = self._inputs['use_gt_layout']
-        use_gt = bool(resolve(use_gt, feeds)) if use_gt is not None else False
-        gt = self._inputs['gt_layout']
-        gt = resolve(gt, feeds) if (gt is not None and use_gt) else None
-        uni = None
-        if self.decoder_sampling and not use_gt:
-            import torch
-            if self._sample_gen is None:
-                self._sample_gen = torch.Generator(device='cpu')
-                self._sample_gen.manual_seed(self.sample_seed)
-            uni = torch.rand((self.T_decoder, N), generator=self._sample_gen).to(self.engine.device)
+        handle.dropout_masks = self.last_masks = self._draw_masks(tr, T, N)
+        mult = tr.multipliers(T, N, self.T_decoder, handle.dropout_masks)
+        uni = self.sampling.draw(self.T_decoder, N, self.engine.device) if self.decoder_sampling and not use_gt \
+            else None
         return self.engine.seq2seq(seq, lens, self.T_decoder, use_gt, gt, uni,
                                    dropout=(mult.get('enc0'), mult.get('dec0')))
 
     # -- eager execution ------------------------------------------------------------------------------
     def run_phase1(self, feeds=None):
-        feeds = feeds or {}
-        seq = resolve(self._inputs['input_seq'], feeds)
-        lens = resolve(self._inputs['seq_len'], feeds)
-        use_gt = self._inputs['use_gt_layout']
-        use_gt = bool(resolve(use_gt, feeds)) if use_gt is not None else False
-        gt = self._inputs['gt_layout']
-        gt = resolve(gt, feeds) if (gt is not None and use_gt) else None
+        seq, lens, use_gt, gt = self.phase1_inputs.resolve(feeds or {})
         return self.engine.seq2seq(seq, lens, self.T_decoder, use_gt, gt)
 
     def run_phase2(self, packed, image_feat, word_vecs):

@@ -65,6 +65,7 @@ class NMN3Model:
             text_seq_batch, seq_length_batch, T_decoder, num_vocab_txt, embed_dim_txt,
             num_vocab_nmn, embed_dim_nmn, lstm_dim, num_layers, assembler, encoder_dropout,
             decoder_dropout, decoder_sampling, use_gt_layout, gt_layout_batch, engine=engine)
+        self.phase1_inputs = self.att_seq2seq.phase1_inputs
         for name in PHASE1_OUTPUTS:
             setattr(self, name, Fetch(self, name, 1))
         self.modules = Modules(image_feat_grid, None, num_choices, engine=engine)

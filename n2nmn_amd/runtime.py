@@ -50,6 +50,40 @@ def resolve(x, feeds):
     return x
 
 
+class Phase1Inputs:
+    """input_seq_batch / seq_length_batch / use_gt_layout / gt_layout_batch of a layout generator's constructor
+    (nmn3_netgen_att.py:46-71): placeholders or values."""
+
+    def __init__(self, input_seq, seq_len, use_gt_layout=None, gt_layout=None):
+        self.input_seq, self.seq_len = input_seq, seq_len
+        self.use_gt_layout, self.gt_layout = use_gt_layout, gt_layout
+
+    def resolve(self, feeds):
+        """-> (input_seq, seq_len, use_gt_layout as a bool, gt_layout or None when it is not used)"""
+        seq = resolve(self.input_seq, feeds)
+        lens = resolve(self.seq_len, feeds)
+        use_gt = bool(resolve(self.use_gt_layout, feeds)) if self.use_gt_layout is not None else False
+        gt = resolve(self.gt_layout, feeds) if (self.gt_layout is not None and use_gt) else None
+        return seq, lens, use_gt, gt
+
+
+class SamplingUniforms:
+    """Stand-in for tf.multinomial's private RNG stream (nmn3_netgen_att.py:216-217): the decoder's [T_dec, N]
+    sampling uniforms, drawn on a seeded host generator so that a seed names the same layouts on every device
+    (the recorded training-driver runs are replayed on another machine)."""
+
+    def __init__(self, seed: int = 0):
+        self.seed = seed
+        self._gen = None
+
+    def draw(self, T_dec: int, N: int, device):
+        import torch
+        if self._gen is None:
+            self._gen = torch.Generator(device='cpu')
+            self._gen.manual_seed(self.seed)
+        return torch.rand((T_dec, N), generator=self._gen).to(device)
+
+
 class _Handle:
     def __init__(self, fetches, feeds):
         self.allowed_fetches = list(fetches)

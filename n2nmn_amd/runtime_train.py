@@ -450,6 +450,10 @@ def _new_trainer(model, plan: LossPlan, op: TrainOp):
     from .train import Trainer
     if hasattr(model, 'new_trainer'):             # a face with its own Trainer (models_vqa: dropout)
         return model.new_trainer(plan, op)
+    s2s = getattr(model, 'att_seq2seq', None)
+    if s2s is not None and (s2s.encoder_dropout or s2s.decoder_dropout):
+        raise NotImplementedError('the CLEVR training step has no LSTM dropout: build the model with '
+                                  'encoder_dropout=decoder_dropout=False (exp_clevr/train_clevr_gt_layout.py:31-32)')
     h = op.optimizer.hyper
     return Trainer(model.engine, weight_decay=plan.weight_decay, lr=h['lr'], beta1=h['beta1'], beta2=h['beta2'],
                    eps=h['eps'], max_grad_l2_norm=op.clip_norm if op.clip_norm is not None else 0.0)
@@ -494,16 +498,19 @@ class TrainStep:
             handle.phase1 = m.run_phase1_training(handle) if hasattr(m, 'run_phase1_training') else \
                 m.run_phase1(handle.feeds)
         tokens = to_numpy(handle.phase1['predicted_tokens'])
-        s2s = getattr(m, 'att_seq2seq', m)._inputs
-        batch = dict(input_seq_batch=resolve(s2s['input_seq'], handle.feeds),
-                     seq_length_batch=resolve(s2s['seq_len'], handle.feeds),
+        seq, lens, _, _ = m.phase1_inputs.resolve(handle.feeds)
+        batch = dict(input_seq_batch=seq, seq_length_batch=lens,
                      image_feat_batch=resolve(m.image_feat_grid, handle.feeds),
                      answer_label_batch=np.asarray(resolve(plan.labels_ph, handle.feeds), np.int32))
         # (the layouts the script assembled and fed back are the tokens of phase 1 -- the ground-truth
         # layout under use_gt_layout, the sampled one otherwise; the Trainer assembles them itself)
         resolve(m.compiler.loom_input_tensor, handle.feeds)           # (must have been fed, like TF's loom input)
         tr = self.trainer
-        scale = tr.forward_backward(batch, tokens, objective=plan.objective)
+        # the keep masks phase 1 of this handle ran under, if the face drew any (models_vqa); a trainer without
+        # dropout sites (CLEVR) is called as before
+        masks = getattr(handle, 'dropout_masks', None)
+        kw = {} if masks is None else dict(dropout=masks)
+        scale = tr.forward_backward(batch, tokens, objective=plan.objective, **kw)
         if plan.validity_ph is not None:
             fed = np.asarray(resolve(plan.validity_ph, handle.feeds), bool)
             if not np.array_equal(fed, np.asarray(tr.last_validity, bool)):

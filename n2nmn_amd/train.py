@@ -25,6 +25,45 @@ def _torch():
 
 
 BWD_DEFER_JOIN = 0x10          # include/n2nmn.h
+# dropout site -> its field of n2nmn_train_io, in the order the multipliers are drawn
+DROPOUT_FIELDS = dict(enc0='drop_enc0', dec0='drop_dec0', qpn_h='drop_qpn_h', qpn_fc1='drop_qpn_fc1')
+
+
+class DropoutStream:
+    """Dropout multipliers (0 or 1 / keep_prob per element) of one model: from {0, 1} keep masks, or drawn
+    on the device from the library's counter-based stream at (seed, offset), each draw taking a fresh
+    stretch of it."""
+
+    def __init__(self, engine: Engine, keep_prob: float = 0.5, seed: int = 0):
+        self.engine = engine
+        self.keep_prob = float(keep_prob)
+        self.seed = int(seed)
+        self.offset = 0
+
+    def multipliers(self, shapes, masks=None):
+        """shapes: ordered {site: shape} of the switched-on sites.  masks None: draw each site in order;
+        False: no dropout ({}); a dict of keep masks: keep / keep_prob for each site it holds (a missing or
+        None site gets no multiplier, a site not in `shapes` is ignored).  Returns float32 device tensors."""
+        torch = _torch()
+        e = self.engine
+        out = {}
+        if masks is False:
+            return out
+        for key, shape in shapes.items():
+            if masks is None:
+                m = torch.empty(shape, dtype=torch.float32, device=e.device)
+                _lib.check(e._lib.n2nmn_dropout_multipliers(m.data_ptr(), m.numel(), self.keep_prob, self.seed,
+                                                            self.offset, e.stream()))
+                self.offset += m.numel()
+            elif masks.get(key) is not None:
+                keep = torch.as_tensor(np.asarray(masks[key], np.float32), device=e.device)
+                if tuple(keep.shape) != tuple(shape):
+                    raise ValueError('dropout mask %s: shape %s, expected %s' % (key, tuple(keep.shape), tuple(shape)))
+                m = (keep / self.keep_prob).contiguous()
+            else:
+                continue
+            out[key] = m
+        return out
 
 
 class GradBuckets:
@@ -197,9 +236,31 @@ class Trainer:
             _lib.check(self._lib.n2nmn_grad_layout(self._ctx, i, C.byref(off), C.byref(n)))
             self.layout[name] = (int(off.value), int(n.value), shape)
         self._keep = None
+        # dropout: site -> switched on (CLEVR: no site); the shapes of the masks follow the reference's dims
+        self.dropout: Dict[str, bool] = {}
+        self.ref_dims = engine.dims
+        self.dropout_stream = DropoutStream(engine)
+        self._mult = None                # the last step's multipliers
 
     # ------------------------------------------------------------------------------------
-    def _io(self, batch, gt_layout, objective: int = 0):
+    def dropout_shapes(self, T: int, N: int, Td: int) -> Dict[str, tuple]:
+        """reference shape of every switched-on dropout site, in the order the multipliers are drawn"""
+        d = self.ref_dims
+        L = d.lstm_dim
+        shapes = dict(enc0=(T, N, L), dec0=(Td, N, L), qpn_h=(N, d.num_layers * L), qpn_fc1=(N, d.qpn_hidden))
+        return {k: shapes[k] for k in DROPOUT_FIELDS if self.dropout.get(k)}
+
+    def _pad_multiplier(self, key: str, m):
+        """reference-shaped multiplier -> the context's layout (identity unless the context pads)"""
+        return m
+
+    def multipliers(self, T: int, N: int, Td: int, dropout=None) -> Dict[str, object]:
+        """this step's dropout multipliers in the context's layout.  dropout: None = drawn from
+        self.dropout_stream; False = none; or a dict of reference-shaped {0, 1} keep masks."""
+        mult = self.dropout_stream.multipliers(self.dropout_shapes(T, N, Td), dropout)
+        return {k: self._pad_multiplier(k, m) for k, m in mult.items()}
+
+    def _io(self, batch, gt_layout, objective: int = 0, dropout=None, mult=None):
         torch = _torch()
         e = self.engine
         d = e.dims
@@ -233,16 +294,24 @@ class Trainer:
             io.lambda_entropy = self.rl['lambda_entropy']
             io.baseline_decay = self.rl['baseline_decay']
             io.baseline = self.baseline.data_ptr()
+        self._mult = self.multipliers(T, N, Td, dropout) if mult is None else mult
+        for key, m in self._mult.items():
+            setattr(io, DROPOUT_FIELDS[key], m.data_ptr())
         self._keep = (seq, lens, feat, labels, gt, packed, val)
         self.last_validity = np.asarray(validity, bool)
         return io, packed, validity
 
-    def forward_backward(self, batch, gt_layout, reduce: bool = True, objective: int = 0) -> float:
+    def forward_backward(self, batch, gt_layout, reduce: bool = True, objective: int = 0, dropout=None) -> float:
         """Forward + both backward phases (+ the bucketed all-reduce).  Afterwards self.grads is
         d total_loss / d variables summed over ranks; returns the 1/world scale.
         objective 0: behavioural cloning on ground-truth layouts; 1: policy gradient, gt_layout
-        then being the layout the decoder sampled for this batch (see step_rl)."""
-        io, packed, _ = self._io(batch, gt_layout, objective)
+        then being the layout the decoder sampled for this batch (see step_rl).
+        dropout: as for multipliers() (None: drawn, if the trainer has dropout sites)."""
+        return self._forward_backward(batch, gt_layout, reduce, objective, dropout)
+
+    def _forward_backward(self, batch, gt_layout, reduce, objective, dropout=None, mult=None) -> float:
+        """mult: ready multipliers (step_rl: the ones the layout was sampled under) instead of `dropout`"""
+        io, packed, _ = self._io(batch, gt_layout, objective, dropout, mult)
         s = self.engine.stream()
         _lib.check(self._lib.n2nmn_train_forward(self._ctx, C.byref(io), packed.handle, s))
         # the decoder's weight gradients and the finish of the late bucket stay on the library's side
@@ -276,23 +345,27 @@ class Trainer:
                                              h['max_grad_l2_norm'], self.iteration,
                                              self.engine.stream()))
 
-    def step(self, batch, gt_layout):
-        scale = self.forward_backward(batch, gt_layout)
+    def step(self, batch, gt_layout, dropout=None):
+        scale = self.forward_backward(batch, gt_layout, dropout=dropout)
         self.apply(scale)
         return self.losses
 
-    def step_rl(self, batch, sample_uniforms, lr: Optional[float] = 1e-4, update: bool = True):
-        """One iteration of exp_clevr/train_clevr_rl_gt_layout.py:183-214: the decoder samples a
-        layout per question (sample_uniforms [T_dec, N] in [0,1) replace tf.multinomial's RNG),
-        the tokens are fetched and assembled on the host (the reference's partial_run does the
-        same), then forward + backward of the policy-gradient loss and an Adam step with the
-        fine-tuning learning rate (lr=None: the trainer's own).  update=False computes the losses and
-        gradients only (no Adam step).  Returns (losses, tokens, expr_validity)."""
-        e = self.engine
-        s2s = e.seq2seq(batch['input_seq_batch'], batch['seq_length_batch'],
-                        sample_uniforms=sample_uniforms)
+    def step_rl(self, batch, sample_uniforms, lr: Optional[float] = 1e-4, update: bool = True, dropout=None):
+        """One iteration of exp_clevr/train_clevr_rl_gt_layout.py:183-214 (exp_vqa/train_vqa_rl_gt_layout.py:
+        150-196): the decoder samples a layout per question (sample_uniforms [T_dec, N] in [0,1) replace
+        tf.multinomial's RNG) under this step's dropout multipliers (the reference samples inside the
+        training graph), the tokens are fetched and assembled on the host (the reference's partial_run
+        does the same), then forward + backward of the policy-gradient loss under the same multipliers
+        and an Adam step with the fine-tuning learning rate (lr=None: the trainer's own).  update=False
+        computes the losses and gradients only (no Adam step).  Returns (losses, tokens, expr_validity)."""
+        torch = _torch()
+        T, N = torch.as_tensor(batch['input_seq_batch']).shape
+        Td = self.ref_dims.T_decoder
+        mult = self.multipliers(T, N, Td, dropout)
+        s2s = self.engine.seq2seq(batch['input_seq_batch'], batch['seq_length_batch'], Td,
+                                  sample_uniforms=sample_uniforms, dropout=(mult.get('enc0'), mult.get('dec0')))
         tokens = s2s['predicted_tokens'].cpu().numpy()
-        scale = self.forward_backward(batch, tokens, objective=1)
+        scale = self._forward_backward(batch, tokens, True, 1, mult=mult)
         if update:               # lr=None: the trainer's own learning rate
             saved = self.hyper['lr']
             self.hyper['lr'] = saved if lr is None else float(lr)

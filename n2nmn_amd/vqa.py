@@ -338,88 +338,30 @@ class VQATrainer(Trainer):
         super().__init__(vqa.engine, weight_decay=weight_decay, lr=lr, max_grad_l2_norm=0.0,
                          dist=dist, rccl=rccl)
         self.vqa = vqa
+        self.ref_dims = vqa.dims
         self.dropout = dict(enc0=encoder_dropout, dec0=decoder_dropout, qpn_h=qpn_dropout,
                             qpn_fc1=qpn_dropout and vqa.dims.qpn_hidden > 0)
-        self.keep_prob = float(keep_prob)
-        self.masks = None            # dict of keep masks for the next step (tests); None: drawn
-        self.seed = 0                # stream of n2nmn_dropout_multipliers; the offset advances
-        self._drawn = 0
-        self._mult = None
-        self._reuse = None
+        self.dropout_stream.keep_prob = float(keep_prob)
 
-    def _multipliers(self, T, N, Td):
-        """Reference-shaped {0, 1} keep masks -> multipliers (0 or 1 / keep_prob) in the context's
-        padded layout (padded hidden units are zero anyway; their multiplier is 0)."""
+    def _pad_multiplier(self, key, m):
+        """reference-shaped multiplier -> the context's padded layout (padded hidden units are zero anyway;
+        their multiplier is 0)"""
         import torch
-        d, di, dev = self.vqa.dims, self.vqa.idims, self.engine.device
-        L, Lp = d.lstm_dim, di.lstm_dim
-        shapes = dict(enc0=(T, N, L), dec0=(Td, N, L), qpn_h=(N, d.num_layers * L),
-                      qpn_fc1=(N, d.qpn_hidden))
-        out = {}
-        for key, on in self.dropout.items():
-            if not on:
-                continue
-            if self.masks is not None:
-                keep = torch.as_tensor(np.asarray(self.masks[key], np.float32), device=dev)
-                if tuple(keep.shape) != shapes[key]:
-                    raise ValueError('dropout mask %s: shape %s, expected %s' %
-                                     (key, tuple(keep.shape), shapes[key]))
-                m = keep / self.keep_prob
-            else:
-                m = torch.empty(shapes[key], dtype=torch.float32, device=dev)
-                _lib.check(self._lib.n2nmn_dropout_multipliers(
-                    m.data_ptr(), m.numel(), self.keep_prob, self.seed, self._drawn,
-                    self.engine.stream()))
-                self._drawn += m.numel()
-            if key in ('enc0', 'dec0'):
-                p = torch.zeros(shapes[key][:2] + (Lp,), device=dev)
-                p[..., :L] = m
-            elif key == 'qpn_h':
-                p = torch.zeros((N, 2 * Lp), device=dev)
-                p[:, :L] = m[:, :L]
-                p[:, Lp:Lp + L] = m[:, L:]
-            else:
-                p = m
-            out[key] = p.contiguous()
-        return out
+        L, Lp = self.vqa.dims.lstm_dim, self.vqa.idims.lstm_dim
+        if key in ('enc0', 'dec0'):
+            p = torch.zeros(tuple(m.shape[:2]) + (Lp,), device=m.device)
+            p[..., :L] = m
+        elif key == 'qpn_h':
+            p = torch.zeros((m.shape[0], 2 * Lp), device=m.device)
+            p[:, :L] = m[:, :L]
+            p[:, Lp:Lp + L] = m[:, L:]
+        else:
+            p = m
+        return p.contiguous()
 
-    def _io(self, batch, gt_layout, objective: int = 0):
-        b = dict(batch)
-        b['image_feat_batch'] = self.vqa.features_with_coords(batch['image_feat_batch'])
-        io, packed, validity = super()._io(b, gt_layout, objective)
-        if self._reuse is None:
-            self._mult = self._multipliers(io.T_enc, io.N, io.T_dec)
-        else:                        # step_rl: the masks the layout was sampled under
-            self._mult, self._reuse = self._reuse, None
-        for key, field in (('enc0', 'drop_enc0'), ('dec0', 'drop_dec0'), ('qpn_h', 'drop_qpn_h'),
-                           ('qpn_fc1', 'drop_qpn_fc1')):
-            if key in self._mult:
-                setattr(io, field, self._mult[key].data_ptr())
-        return io, packed, validity
-
-    def step_rl(self, batch, sample_uniforms, lr=1e-4, update: bool = True):
-        """One iteration of exp_vqa/train_vqa_rl_gt_layout.py:150-196: the layout is sampled from the
-        network WITH this step's dropout masks (the reference samples inside the training graph),
-        fetched and assembled on the host, then the policy-gradient loss (:106-126, every layout
-        counted as valid like :112) is differentiated under the same masks."""
-        import torch
-        e = self.engine
-        seq = torch.as_tensor(batch['input_seq_batch'])
-        T, N = seq.shape
-        mult = self._multipliers(T, N, self.vqa.dims.T_decoder)
-        s2s = e.seq2seq(batch['input_seq_batch'], batch['seq_length_batch'], self.vqa.dims.T_decoder,
-                        sample_uniforms=sample_uniforms,
-                        dropout=(mult.get('enc0'), mult.get('dec0')))
-        tokens = s2s['predicted_tokens'].cpu().numpy()
-        self._reuse = mult
-        scale = self.forward_backward(batch, tokens, objective=1)
-        if update:
-            saved = self.hyper['lr']
-            self.hyper['lr'] = saved if lr is None else float(lr)
-            self.apply(scale)
-            self.hyper['lr'] = saved
-        validity = self._keep[6].cpu().numpy().astype(bool) if self._keep[6] is not None else None
-        return self.losses, tokens, validity
+    def _io(self, batch, *args):
+        b = dict(batch, image_feat_batch=self.vqa.features_with_coords(batch['image_feat_batch']))
+        return super()._io(b, *args)
 
     def gradients_reference_shaped(self):
         """name -> numpy gradient in the reference's (unpadded) variable shape."""

@@ -15,6 +15,7 @@ from oracle import n2nmn_oracle as O
 from n2nmn_amd import _lib
 from n2nmn_amd.nmn3_assembler import OP_CODE
 from n2nmn_amd.spec import Dims
+from n2nmn_amd.train import Trainer
 
 _OP_NAME = {v: k for k, v in OP_CODE.items()}
 
@@ -120,7 +121,7 @@ class OracleTrainer:
             X = X + a.P[tokens[t]]
         return out
 
-    def forward_backward(self, batch, gt_layout, reduce=True, objective=0):
+    def forward_backward(self, batch, gt_layout, reduce=True, objective=0, dropout=None):
         G, e = self.G, self.engine
         tokens = np.asarray(gt_layout, np.int32)
         names = list(e.assembler.module_names)
@@ -176,7 +177,7 @@ class _OracleVQASeq2Seq:
 
     def seq2seq(self, input_seq, seq_len, T_dec=None, use_gt_layout=False, gt_layout=None, sample_uniforms=None,
                 forced_tokens=None, dropout=None, **kw):
-        """dropout: (layer-0 output multipliers of the encoder, of the decoder) as VQATrainer._multipliers makes them
+        """dropout: (layer-0 output multipliers of the encoder, of the decoder) as VQATrainer.multipliers makes them
         (0 or 1 / keep_prob): the training face's phase 1"""
         o = self.o
         o.calls['seq2seq'] += 1
@@ -258,22 +259,24 @@ class OracleVQATrainer(OracleTrainer):
                  decoder_dropout=True, qpn_dropout=True, keep_prob=0.5):
         super().__init__(vqa, weight_decay=weight_decay, lr=lr, max_grad_l2_norm=0.0)
         self.vqa = vqa
+        self.ref_dims = vqa.dims
         self.dropout = dict(enc0=encoder_dropout, dec0=decoder_dropout, qpn_h=qpn_dropout,
                             qpn_fc1=qpn_dropout and vqa.dims.qpn_hidden > 0)
         assert keep_prob == 0.5
-        self.masks = None
-        self._reuse = None
         self.mask_history = []       # the keep masks of every step (the recording stores their checksums)
 
-    def _multipliers(self, T, N, Td):
-        assert self.masks is not None, 'the face hands the masks of a handle to the trainer'
-        return {k: np.asarray(v, np.float64) * 2.0 for k, v in self.masks.items() if self.dropout.get(k)}
+    dropout_shapes = Trainer.dropout_shapes
 
-    def forward_backward(self, batch, gt_layout, reduce=True, objective=0):
+    def multipliers(self, T, N, Td, dropout=None):
+        assert isinstance(dropout, dict), 'the face hands the masks of a handle to the trainer'
+        return {k: np.asarray(v, np.float64) * 2.0 for k, v in dropout.items() if self.dropout.get(k)}
+
+    def forward_backward(self, batch, gt_layout, reduce=True, objective=0, dropout=None):
         G, e = self.G, self.engine
         tokens = np.asarray(gt_layout, np.int32)
-        mult, self._reuse = self._reuse, None
-        assert mult is not None, 'phase 1 of the handle draws the masks (models_vqa.NMN3Model.run_phase1_training)'
+        assert dropout is not None, 'phase 1 of the handle draws the masks (models_vqa.NMN3Model.run_phase1_training)'
+        T, N = np.shape(batch['input_seq_batch'])
+        mult = self.multipliers(T, N, tokens.shape[0], dropout)
         masks = {k: (np.asarray(v) > 0).astype(np.float64) for k, v in mult.items()}
         self.mask_history.append(masks)
         b = {k: np.asarray(v) for k, v in batch.items()}

@@ -59,8 +59,7 @@ def test_vqa_training_step_with_dropout_matches_reference_code(setup, fx):
     z, meta = fx
     m = meta['vqa_train']
     eng.load_weights(w)
-    tr.masks = FC.vqa_dropout_masks(d)
-    tr.forward_backward(batch, gt, reduce=False)
+    tr.forward_backward(batch, gt, reduce=False, dropout=FC.vqa_dropout_masks(d))
     assert_close('scores', t2n(tr.scores), z['vqa_train/scores'], 1e-4)
     ls = t2n(tr.losses)
     for i, k in enumerate(('avg_sample_loss', 'seq_likelihood_loss')):
@@ -93,12 +92,7 @@ def test_vqa_training_without_dropout_equals_plain_forward(setup, fx):
     d, batch, gt, eng, tr, w = setup
     z, meta = fx
     eng.load_weights(w)
-    saved = dict(tr.dropout)
-    tr.dropout = {k: False for k in saved}
-    try:
-        tr.forward_backward(batch, gt, reduce=False)
-    finally:
-        tr.dropout = saved
+    tr.forward_backward(batch, gt, reduce=False, dropout=False)
     assert_close('scores', t2n(tr.scores), z['vqa_gt/scores'], 1e-4)
     assert np.isfinite(t2n(tr.grads)).all()
 
@@ -106,7 +100,6 @@ def test_vqa_training_without_dropout_equals_plain_forward(setup, fx):
 def test_drawn_masks_keep_about_half(setup):
     d, batch, gt, eng, tr, w = setup
     eng.load_weights(w)
-    tr.masks = None
     tr.forward_backward(batch, gt, reduce=False)
     m = tr._mult['enc0'][..., :d.lstm_dim]
     frac = float((m > 0).float().mean())
@@ -137,10 +130,9 @@ def test_vqa_policy_gradient_step_with_dropout_matches_oracle(setup):
     d, batch, gt, eng, tr, w = setup
     eng.load_weights(w)
     masks = FC.vqa_dropout_masks(d)
-    tr.masks = masks
     tr.baseline.fill_(1.25)
     uni = np.random.default_rng(3).random((d.T_decoder, d.N)).astype(np.float32)
-    losses, tokens, validity = tr.step_rl(batch, uni, update=False)
+    losses, tokens, validity = tr.step_rl(batch, uni, update=False, dropout=masks)
     losses = t2n(losses)
     assert validity.all()
     asm = eng.assembler

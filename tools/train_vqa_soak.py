@@ -19,7 +19,7 @@ def main(steps=200):
     eng = vqa.VQAEngine(d)
     eng.load_weights(synth.make_weights_from_shapes(vqa.vqa_variable_shapes(d), seed=0))
     tr = vqa.VQATrainer(eng)
-    tr.seed = 7
+    tr.dropout_stream.seed = 7
     dev = eng.engine.device
     layouts = (['_Find', '_Describe'], ['_Find', '_Find', '_And', '_Describe'],
                ['_Find', '_Transform', '_Describe'], ['_Find', '_Transform', '_Find', '_And', '_Describe'])
