@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """Benchmark of the N2NMN CLEVR forward hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: the script re-executes itself under torch.distributed.run, one rank per GPU; when the
      driver already launched it that way, RANK / LOCAL_RANK / WORLD_SIZE come from the environment)
+
+A plain run does only what the headline figure needs: set-up, the warm-up passes, the `--steps` timed
+passes, the `--dump-outputs` arrays and the result line.  `--full` adds, after the timed region, everything
+else this script measures or checks: `parity_check`, `single_batch`, `config3`, `eos_retire`, `bf16x3`,
+the per-kernel `roofline` / `roofline_attention` / `kernels` tables, `config4` / `config5` and
+`cpu_baseline` (for `--config 4 | 5 | 6`: their kernel tables, CPU baseline and extra passes).
+`--no-profile` / `--no-cpu-baseline` leave parts of it out again.
 
 One "step" = ONE PASS of the hot path (BASELINE.json configs[1]: CLEVR forward, fixed ground-truth
 layouts, 10x15x512 synthetic pool5 features) over `--inflight K` client batches of 64 questions that
@@ -19,11 +26,12 @@ exactly `--steps` passes are timed, split evenly over the workers; value = K * 6
 `config` says what a launch carried (`rows_per_launch`, `questions_in_flight`).  Default: 2 streams,
 K = 16 (1024 rows per launch; round 5's sweep: 2 / 3 / 4 streams = 311 / 316 / 301 k questions/s -- 3 is not
 the default because the 3-worker form of tests/test_gpu_bench_config.py failed in 2 of 5 runs in the bf16x3
-mode -- a 3e-4 logit error on one worker's pass, not reproduced in isolation: profiles/r05_notes.md section 8).  `parity_check`: logits of the timed passes against the oracle.
+mode -- a 3e-4 logit error on one worker's pass, not reproduced in isolation: profiles/r05_notes.md section 8).
+With `--full`: `parity_check`: logits of the timed passes against the oracle.
 Latency number (`single_batch`): one batch of 64 in flight (the strict reading of "batch 64").
 `config3`: the same with layouts chosen by the greedy decoder (BASELINE.json configs[2]).
 `config4` / `config5`: the training step and the models_vqa forward (BASELINE.json configs[3], [4]),
-one GPU, so the driver's default line carries them too (`--config 4|5|6` runs them alone).
+one GPU, so the `--full` line carries them too (`--config 4|5|6` runs them alone).
 
 Inputs are resident in HBM before the timed region.  Multi-GPU: the path shards by question with no
 data-path collective (weak scaling: every rank runs its own stream of batches); timing =
@@ -57,7 +65,7 @@ MFMA_F32_PEAK_TF = 157.3    # MI355X_MICROARCH.md: fp32-input MFMA dense peak
 MFMA_FAMILIES = ('lstm_step', 'gemm_pk', 'lstm_bwd_step', 'gemm_tn')
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=200)
@@ -76,25 +84,30 @@ def parse():
     ap.add_argument('--host-assemble', action='store_true',
                     help='reference flow: token fetch + C++ Assembler + level scheduler instead of '
                          'the on-device layout walker')
-    ap.add_argument('--plain', action='store_true',
-                    help='only the timed throughput region (no single_batch / config3 / per-kernel pass / '
-                         'cpu baseline): the command the rocprofv3 traces in profiles/ are taken from')
+    extent = ap.add_mutually_exclusive_group()
+    extent.add_argument('--full', action='store_true',
+                        help='after the timed region, also run every other measurement and check of this '
+                             'script (oracle parity, single batch, config3, eos_retire, bf16x3, per-kernel '
+                             'tables, config4 / config5, cpu baseline); off: the headline figure alone')
+    extent.add_argument('--plain', action='store_true',
+                        help='only the timed throughput region: what a run without --full does (kept for the '
+                             'commands the rocprofv3 traces in profiles/ were taken with)')
     ap.add_argument('--lstm-mode', default=None, choices=(None, 'throughput', 'throughput_bf16x3'),
                     help="recurrent-step mode of the timed passes; 'throughput_bf16x3' = the opt-in "
                          "split-operand bf16 mode (NOT the headline: `dtype` then reads 'bf16x3 (fp32-"
-                         "equivalent)'; the default line reports it under the `bf16x3` key)")
+                         "equivalent)'; the --full line reports it under the `bf16x3` key)")
     ap.add_argument('--eos-retire', action='store_true',
                     help='timed passes with the inference option N2NMN_S2S_EOS_RETIRE (NOT the headline: the '
-                         'metric text and config.eos_retire say so; the default line reports it under the '
+                         'metric text and config.eos_retire say so; the --full line reports it under the '
                          '`eos_retire` key).  For rocprofv3 traces of the retired pass')
     ap.add_argument('--layouts', default='templates', choices=('templates', 'clevr_like'),
                     help="ground-truth layout mix of the timed passes ('clevr_like': synth.clevr_like_layout_batch)")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-profile', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: no cpu_baseline')
+    ap.add_argument('--no-profile', action='store_true', help='with --full: no per-kernel tables')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed passes, write what the last timed pass of every worker computed '
                          '(scores, tokens, validity; rank 0) as DIR/<name>.npy (--config 2 / 3)')
-    return ap.parse_args()
+    return ap.parse_args(argv)
 
 
 PMC_FILE = os.path.join(ROOT, 'profiles', 'r06_pmc_traffic.json')
@@ -355,8 +368,8 @@ def train_numbers(args, dp, local_rank, steps, warmup, profile=True, cpu=True):
 
 
 def bench_vqa(args, dp, local_rank):
-    out = vqa_numbers(args, dp, local_rank, args.steps, args.warmup, not args.no_profile)
-    if args.batch == 64:
+    out = vqa_numbers(args, dp, local_rank, args.steps, args.warmup, not args.no_profile, per_pass_coords=args.full)
+    if args.full and args.batch == 64:
         p = vqa_numbers(args, dp, local_rank, max(3, args.steps // 8), 2, False, batches_per_pass=8)
         if dp.rank == 0:
             out['passes'] = {k: p[k] for k in ('metric', 'value', 'unit', 'ms_per_step', 'steps', 'config')}
@@ -371,13 +384,14 @@ def bench_vqa(args, dp, local_rank):
 
 
 def vqa_numbers(args, dp, local_rank, steps, warmup, profile=True, batches_per_pass=1, lstm_mode=None,
-                device_layouts=False, eos_retire=False):
+                device_layouts=False, eos_retire=False, per_pass_coords=True):
     """BASELINE.json configs[4]: models_vqa forward (exp_vqa/eval_vqa2.py:103-137) -- seq2seq with
     the 17742-word vocabulary and lstm_dim 1000, coordinate map, the 4-module network at map_dim
     1024 on 14x14x2048 features, question prior net -- batch 128 per GPU, ground-truth layouts from
     the v2 validation histogram.  batches_per_pass > 1: that many client batches of 128
     as one pass (every launch carries batches_per_pass * 128 rows; recurrent step in 'throughput'
-    mode), the serving form of the headline configuration."""
+    mode), the serving form of the headline configuration.  per_pass_coords: time the single-batch passes a
+    second time with the coordinate channels appended per pass (`with_per_pass_add_coords`)."""
     import numpy as np
     import torch
     from n2nmn_amd import synth, vqa
@@ -432,7 +446,7 @@ def vqa_numbers(args, dp, local_rank, steps, warmup, profile=True, batches_per_p
     # (models_vqa/nmn3_modules.py:11-31, inside the reference's graph) is then done per pass by n2nmn_add_coords --
     # the figure comparable with rounds 1-4
     elapsed_coords = None
-    if batches_per_pass == 1 and not device_layouts and not eos_retire:
+    if per_pass_coords and batches_per_pass == 1 and not device_layouts and not eos_retire:
         slabs = batches
         batches = [dict(b, image_feat_batch=b['image_feat_batch'][..., :d.D].contiguous()) for b in slabs]
         run_steps(0, warmup)
@@ -687,11 +701,11 @@ def layout_work(tokens, names):
 
 def main():
     args = parse()
-    if args.plain:
+    if not args.full:
         args.no_profile = args.no_cpu_baseline = True
     elif args.eos_retire or args.layouts != 'templates':
-        sys.exit('bench.py: --eos-retire / --layouts are for --plain runs (tracing); the default line carries '
-                 'the option and both mixes under its `eos_retire` key')
+        sys.exit('bench.py: --eos-retire / --layouts are for runs without --full (tracing); the --full line '
+                 'carries the option and both mixes under its `eos_retire` key')
     if args.dump_outputs and args.config not in (2, 3):
         sys.exit('bench.py: --dump-outputs writes the outputs of the forward passes (--config 2 / 3)')
     ensure_world(args, sys.argv[1:])
@@ -799,7 +813,7 @@ def main():
         }
         # ---- what the timed passes computed, against the oracle: slot 0 of the bucket each worker
         # ran last (fp32 batched port, pinned to the reference's code through the numpy oracle)
-        if world == 1 and not args.plain:
+        if world == 1 and args.full:
             from oracle import n2nmn_oracle_batched as OB
             torch.set_num_threads(min(16, torch.get_num_threads()))
             wt = OB.to_torch(w, torch.float64)
@@ -831,7 +845,7 @@ def main():
         sync()
         return (time.perf_counter() - t0) / n
 
-    if rank == 0 and not args.plain:
+    if rank == 0 and args.full:
         # ---- one batch of d.N questions in flight (latency-oriented number), same code path
         one = dict(input_seq_batch=sb.input_seq[:, :d.N].contiguous(), seq_length_batch=sb.seq_length[:d.N],
                    image_feat_batch=sb.image_feat[:d.N])
@@ -899,7 +913,7 @@ def main():
     # tokens) and CLEVR-like layouts of up to 19 tokens (n2nmn_amd/synth.py: the reference's linearisation
     # rules, exp_clevr/data/get_ground_truth_layout.py:4-37,49-96, applied to the CLEVR question families),
     # each against the full decoder on the SAME layouts; logits of the retired passes against the oracle.
-    if rank == 0 and not args.plain and use_gt and K > 1 and pipe.mode.startswith('throughput'):
+    if rank == 0 and args.full and use_gt and K > 1 and pipe.mode.startswith('throughput'):
         from oracle import n2nmn_oracle_batched as OB
         torch.set_num_threads(min(16, torch.get_num_threads()))
         wt64 = OB.to_torch(w, torch.float64)
@@ -990,7 +1004,7 @@ def main():
     # ---- opt-in split-operand bf16 mode (N2NMN_MODE_THROUGHPUT_BF16X3): the same passes with the
     # recurrent contraction on bf16 MFMAs over three-way split operands, its logits against the oracle.
     # Reported beside the headline, never as the headline (include/n2nmn.h).
-    if rank == 0 and not args.plain and use_gt and K > 1 and pipe.mode == 'throughput':
+    if rank == 0 and args.full and use_gt and K > 1 and pipe.mode == 'throughput':
         try:
             for wk in pipe.workers:
                 wk['engine'].set_mode('throughput_bf16x3')
@@ -1224,8 +1238,8 @@ def main():
                                      'FindSameProperty reads its own map and the feature map' %
                                      (HW * D * 4, HW * Mp * 4)}
 
-    # ---- BASELINE.json configs[3] / configs[4] beside the headline, so the driver's line carries them
-    if world == 1 and not args.plain and use_gt and args.batch == 64:
+    # ---- BASELINE.json configs[3] / configs[4] beside the headline, so the --full line carries them
+    if world == 1 and args.full and use_gt and args.batch == 64:
         sync()
         c4 = train_numbers(args, dp, local_rank, 30, 5, profile=True, cpu=False)
         out['config4'] = {k: c4[k] for k in ('metric', 'value', 'unit', 'ms_per_step', 'steps', 'config',

@@ -6,6 +6,8 @@ import subprocess
 import sys
 import types
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -58,8 +60,45 @@ def test_stdout_carries_only_the_result_line():
     assert 'library noise' in r.stderr and 'raw noise on fd 1' in r.stderr
 
 
+def test_full_is_opt_in():
+    """`--full` (every measurement and check beside the headline) is off unless asked for; `--plain` names the
+    default and cannot be combined with it."""
+    import bench
+    assert not bench.parse(['--gpus', '1', '--steps', '20', '--warmup', '5']).full
+    assert bench.parse(['--gpus', '1', '--steps', '20', '--warmup', '5', '--full']).full
+    with pytest.raises(SystemExit):
+        bench.parse(['--full', '--plain'])
+
+
+# what only a --full run reports
+FULL_ONLY = ('parity_check', 'single_batch', 'config3', 'eos_retire', 'bf16x3', 'roofline', 'roofline_attention',
+             'kernels', 'gpu_us_per_step', 'config4', 'config5', 'cpu_baseline')
+
+
+@pytest.mark.gpu
+def test_plain_run_reports_the_headline_alone(tmp_path):
+    """A run without --full: the headline figures of exactly --steps timed passes and the --dump-outputs
+    arrays, nothing of what --full adds."""
+    import json
+    import numpy as np
+    p = _run({}, '--gpus', '1', '--steps', '4', '--warmup', '2', '--dump-outputs', str(tmp_path))
+    assert p.returncode == 0, p.stderr[-4000:]
+    lines = p.stdout.splitlines()
+    assert len(lines) == 1, p.stdout
+    line = json.loads(lines[0])
+    assert line['unit'] == 'questions/sec' and line['higher_is_better'] is True and line['dtype'] == 'f32'
+    assert line['steps'] == 4 and line['warmup'] == 2 and line['n_gpus'] == 1
+    assert line['value'] > 0 and line['ms_per_step'] > 0
+    assert line['metric'].startswith('questions/sec (forward) on CLEVR')
+    for k in FULL_ONLY:
+        assert k not in line, k
+    rows = line['config']['rows_per_launch']
+    sc = np.load(str(tmp_path / 'scores.npy'))
+    assert sc.dtype == np.float32 and sc.shape[0] == 2 * rows and np.isfinite(sc).all()
+
+
 def test_result_line_fits_a_short_stdout_tail():
-    """The full report of a default run (profiles/r06_bench_steps20.json, 22 KB) goes to stderr; the stdout line
+    """The full report of a --full run (profiles/r06_bench_steps20.json, 22 KB) goes to stderr; the stdout line
     keeps the headline, `config`, `parity_check`, `roofline`, `cpu_baseline` and the figures of every sub-report
     in a few KB."""
     import json

@@ -17,8 +17,8 @@ rocprofv3 --kernel-trace --stats -d $O/r02_q_trace1 -- $CMD1 > /dev/null 2>&1
 python /root/repo/tools/rocprof_summary.py $(ls $O/r02_q_trace1/*/*.db | head -1) > $O/r02_q_kernel_stats_single_batch.txt
 rm -rf $O/r02_q_fetch $O/r02_q_write $O/r02_q_trace8 $O/r02_q_trace1
 cd /root/repo
-python bench.py > $O/r02_q_bench.json 2> $O/r02_q_bench.err
-python bench.py --steps 20 --warmup 5 > $O/r02_q_bench_steps20.json 2>/dev/null
+python bench.py --full > $O/r02_q_bench.json 2> $O/r02_q_bench.err
+python bench.py --steps 20 --warmup 5 --full > $O/r02_q_bench_steps20.json 2>/dev/null
 tail -c 300 $O/r02_q_bench.err
 head -12 $O/r02_q_kernel_stats_inflight8.txt
 head -10 $O/r02_q_kernel_stats_single_batch.txt

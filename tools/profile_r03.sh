@@ -29,14 +29,14 @@ python /root/repo/tools/rocprof_summary.py $DB4 > $O/r03_train_kernel_stats.txt
 python /root/repo/tools/trace_step.py $DB4 grad_sqnorm > $O/r03_train_step_trace.txt
 rm -rf $O/r03_fetch $O/r03_write $O/r03_tr16 $O/r03_tr2x16 $O/r03_tr1 $O/r03_tr4
 cd /root/repo
-python bench.py --config 4 --steps 100 --warmup 10 > $O/r03_train_bench.json 2>/dev/null
-python bench.py --config 5 --steps 20 --warmup 3 --no-cpu-baseline > $O/r03_vqa_bench.json 2>/dev/null
+python bench.py --config 4 --steps 100 --warmup 10 --full > $O/r03_train_bench.json 2>/dev/null
+python bench.py --config 5 --steps 20 --warmup 3 --no-cpu-baseline --full > $O/r03_vqa_bench.json 2>/dev/null
 # the driver's multi-GPU launch form, one rank (full line incl. config4 / config5)
 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 \
-    bench.py --gpus 1 --steps 20 --warmup 5 > $O/r03_bench_torchrun1.json 2> $O/r03_bench_torchrun1.err
+    bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/r03_bench_torchrun1.json 2> $O/r03_bench_torchrun1.err
 tail -c 400 $O/r03_bench_torchrun1.json
-python bench.py > $O/r03_bench.json 2> $O/r03_bench.err
-python bench.py --steps 20 --warmup 5 > $O/r03_bench_steps20.json 2>/dev/null
+python bench.py --full > $O/r03_bench.json 2> $O/r03_bench.err
+python bench.py --steps 20 --warmup 5 --full > $O/r03_bench_steps20.json 2>/dev/null
 tail -c 300 $O/r03_bench.err
 head -14 $O/r03_kernel_stats_1x16.txt
 head -8 $O/r03_kernel_stats_single_batch.txt

@@ -27,18 +27,18 @@ rocprofv3 --kernel-trace --stats -d $O/${T}_tr4 -- $CMD4 > /dev/null 2>&1
 DB4=$(ls $O/${T}_tr4/*/*.db | head -1)
 python /root/repo/tools/rocprof_summary.py $DB4 > $O/${T}_train_kernel_stats.txt
 python /root/repo/tools/trace_step.py $DB4 grad_sqnorm > $O/${T}_train_step_trace.txt
-CMD5="python /root/repo/bench.py --config 5 --steps 24 --warmup 2 --no-profile"
+CMD5="python $(dirname $O)/bench.py --config 5 --steps 24 --warmup 2 --no-profile --full"
 rocprofv3 --kernel-trace --stats -d $O/${T}_tr5 -- $CMD5 > /dev/null 2>&1
 python /root/repo/tools/rocprof_summary.py $(ls $O/${T}_tr5/*/*.db | head -1) > $O/${T}_config5_kernel_stats.txt
 rm -rf $O/${T}_fetch $O/${T}_write $O/${T}_tr16 $O/${T}_trb3 $O/${T}_tr2x16 $O/${T}_tr1 $O/${T}_tr4 $O/${T}_tr5
 cd /root/repo
 cp $O/${T}_pmc_traffic.json /root/repo/profiles/r04_pmc_traffic.json    # (so that the bench runs below quote it)
-python bench.py --config 4 --steps 100 --warmup 10 > $O/${T}_train_bench.json 2>/dev/null
-python bench.py --config 5 --steps 24 --warmup 3 --no-cpu-baseline > $O/${T}_vqa_bench.json 2>/dev/null
+python bench.py --config 4 --steps 100 --warmup 10 --full > $O/${T}_train_bench.json 2>/dev/null
+python bench.py --config 5 --steps 24 --warmup 3 --no-cpu-baseline --full > $O/${T}_vqa_bench.json 2>/dev/null
 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 \
-    bench.py --gpus 1 --steps 20 --warmup 5 > $O/${T}_bench_torchrun1.json 2> $O/${T}_bench_torchrun1.err
-python bench.py > $O/${T}_bench.json 2> $O/${T}_bench.err
-python bench.py --steps 20 --warmup 5 > $O/${T}_bench_steps20.json 2>/dev/null
-python bench.py --steps 20 --warmup 5 --lstm-mode throughput_bf16x3 > $O/${T}_bench_steps20_bf16x3.json 2>/dev/null
+    bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/${T}_bench_torchrun1.json 2> $O/${T}_bench_torchrun1.err
+python bench.py --full > $O/${T}_bench.json 2> $O/${T}_bench.err
+python bench.py --steps 20 --warmup 5 --full > $O/${T}_bench_steps20.json 2>/dev/null
+python bench.py --steps 20 --warmup 5 --lstm-mode throughput_bf16x3 --full > $O/${T}_bench_steps20_bf16x3.json 2>/dev/null
 tail -c 300 $O/${T}_bench.err
 ls -la $O | grep ${T}

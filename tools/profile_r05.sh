@@ -30,17 +30,17 @@ trace kernel_stats_single_batch python $R/bench.py --plain --streams 1 --infligh
 trace train_kernel_stats python $R/bench.py --config 4 --steps 20 --warmup 3 --no-cpu-baseline --no-profile
 python $R/tools/trace_step.py $DB grad_sqnorm > $O/${T}_train_step_trace.txt
 rm -rf $O/${T}_tr
-trace config5_kernel_stats python $R/bench.py --config 5 --steps 24 --warmup 2 --no-profile; rm -rf $O/${T}_tr
+trace config5_kernel_stats python $R/bench.py --config 5 --steps 24 --warmup 2 --no-profile --full; rm -rf $O/${T}_tr
 rm -rf $O/${T}_fetch $O/${T}_write
 cd $R
 cp $O/${T}_pmc_traffic.json $R/profiles/r05_pmc_traffic.json    # (so that the bench runs below quote it)
 timeout 150 python tools/walk_stage_bench.py templates 2>&1 | grep -v amdgpu.ids > $O/${T}_walk_stage_templates.txt
 timeout 150 python tools/walk_stage_bench.py clevr_like 2>&1 | grep -v amdgpu.ids > $O/${T}_walk_stage_clevr_like.txt
-timeout 200 python bench.py --config 4 --steps 100 --warmup 10 > $O/${T}_train_bench.json 2>/dev/null
-timeout 300 python bench.py --config 5 --steps 24 --warmup 3 --no-cpu-baseline > $O/${T}_vqa_bench.json 2>/dev/null
+timeout 200 python bench.py --config 4 --steps 100 --warmup 10 --full > $O/${T}_train_bench.json 2>/dev/null
+timeout 300 python bench.py --config 5 --steps 24 --warmup 3 --no-cpu-baseline --full > $O/${T}_vqa_bench.json 2>/dev/null
 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 \
-    bench.py --gpus 1 --steps 20 --warmup 5 > $O/${T}_bench_torchrun1.json 2> $O/${T}_bench_torchrun1.err
-timeout 300 python bench.py --steps 20 --warmup 5 --lstm-mode throughput_bf16x3 --no-cpu-baseline > $O/${T}_bench_steps20_bf16x3.json 2>/dev/null
-timeout 600 python bench.py --steps 20 --warmup 5 > $O/${T}_bench_steps20.json 2> $O/${T}_bench_steps20.err
-timeout 900 python bench.py > $O/${T}_bench.json 2> $O/${T}_bench.err
+    bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/${T}_bench_torchrun1.json 2> $O/${T}_bench_torchrun1.err
+timeout 300 python bench.py --steps 20 --warmup 5 --lstm-mode throughput_bf16x3 --no-cpu-baseline --full > $O/${T}_bench_steps20_bf16x3.json 2>/dev/null
+timeout 600 python bench.py --steps 20 --warmup 5 --full > $O/${T}_bench_steps20.json 2> $O/${T}_bench_steps20.err
+timeout 900 python bench.py --full > $O/${T}_bench.json 2> $O/${T}_bench.err
 ls -la $O | grep $T

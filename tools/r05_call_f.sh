@@ -16,5 +16,5 @@ import json,sys
 o=json.loads(sys.stdin.read()); print('chunks=$CH', o['value'], o['ms_per_step'])" >> $O/train_sweep.log 2>&1
 done
 cat $O/train_sweep.log
-timeout 500 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+timeout 500 python bench.py --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err
 tail -c 300 $O/bench.err

@@ -9,7 +9,7 @@ timeout 150 python tools/walk_stage_bench.py templates 2>&1 | grep -v amdgpu.ids
 timeout 150 python tools/walk_stage_bench.py clevr_like 2>&1 | grep -v amdgpu.ids | tee $O/stage_clevr_like.log
 (cd /tmp && export TMPDIR=/tmp && timeout 200 rocprofv3 --kernel-trace --stats -d $O/tr16 -- python $GRAFT_REPO_ROOT/bench.py --plain --streams 1 --inflight 16 --steps 12 --warmup 2 > /dev/null 2>&1; python $GRAFT_REPO_ROOT/tools/rocprof_summary.py $(ls $O/tr16/*/*.db | head -1) > $O/kernel_stats_1x16.txt; rm -rf $O/tr16)
 grep -i "walk" $O/kernel_stats_1x16.txt
-timeout 600 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+timeout 600 python bench.py --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err
 tail -c 400 $O/bench.err
 python - <<'P'
 import json

@@ -7,7 +7,7 @@ cd $R
 timeout 1200 python -m pytest tests -q -m gpu --timeout 300 > $O/${T}_pytest_all.log 2>&1
 grep -n "passed\|failed" $O/${T}_pytest_all.log | tail -3
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/${T}_bench_steps20.json 2> $O/${T}_bench_steps20.err
+timeout 900 python bench.py --steps 20 --warmup 5 --full > $O/${T}_bench_steps20.json 2> $O/${T}_bench_steps20.err
 python - <<'P'
 import json
 o=json.loads(open('/root/repo/gpurun_out/r05w_bench_steps20.json').read().strip().splitlines()[-1])

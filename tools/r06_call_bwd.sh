@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r06bwd; mkdir -p $O
 cd $R
 timeout 900 python -m pytest tests/test_gpu_train.py tests/test_gpu_train_kernels.py tests/test_gpu_train_dp.py tests/test_gpu_train_rl.py tests/test_gpu_vqa_train.py tests/test_gpu_train_driver_trace.py -x -q 2>&1 | tail -8 > $O/train_tests.log
 cat $O/train_tests.log
-timeout 200 python bench.py --config 4 --steps 100 --warmup 10 --no-cpu-baseline > $O/train_bench.json 2> $O/train_bench.err
+timeout 200 python bench.py --config 4 --steps 100 --warmup 10 --no-cpu-baseline --full > $O/train_bench.json 2> $O/train_bench.err
 python -c "
 import json
 d=json.loads(open('$O/train_bench.json').read().strip().splitlines()[-1])

@@ -17,7 +17,7 @@ print('RESULT $1 rep $rep: ms_per_step', d.get('ms_per_step'))
 for v in 0 4 2 3; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -DFWS_NS=$v -I include -c n2nmn_amd/csrc/kernels_seq2seq.hip -o n2nmn_amd/lib/obj/kernels_seq2seq.hip.o || exit 1
   run fwd_ns$v
-  timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-profile > $O/fb_$v.json 2> $O/fb.err
+  timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-profile --full > $O/fb_$v.json 2> $O/fb.err
   python -c "
 import json
 d=json.loads(open('$O/fb_$v.json').read().strip().splitlines()[-1])

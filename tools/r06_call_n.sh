@@ -3,7 +3,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r06n; mkdir -p $O
 cd $R
 timeout 900 python -m pytest tests/test_gpu_train.py tests/test_gpu_train_kernels.py tests/test_gpu_train_dp.py tests/test_gpu_train_rl.py tests/test_gpu_vqa_train.py tests/test_gpu_reference_fixture.py tests/test_gpu_train_driver_trace.py tests/test_gpu_eos_retire.py -x -q 2>&1 | tail -8 > $O/train_tests.log
 cat $O/train_tests.log
-timeout 200 python bench.py --config 4 --steps 100 --warmup 10 --no-cpu-baseline > $O/train_bench_ks.json 2> $O/train_bench_ks.err
+timeout 200 python bench.py --config 4 --steps 100 --warmup 10 --no-cpu-baseline --full > $O/train_bench_ks.json 2> $O/train_bench_ks.err
 python -c "
 import json,sys
 d=json.loads(open('$O/train_bench_ks.json').read().strip().splitlines()[-1])

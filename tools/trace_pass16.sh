@@ -8,7 +8,7 @@ rm -rf $O/tr1
 head -16 $O/r03_b_kernel_stats_1x16.txt
 awk 'NR<=3 || NR%3==0' $O/r03_b_pass_trace_1x16.txt | head -40
 cd /root/repo
-python bench.py --streams 2 --inflight 16 --steps 20 --warmup 4 --no-cpu-baseline 2>/dev/null | python -c "
+python bench.py --streams 2 --inflight 16 --steps 20 --warmup 4 --no-cpu-baseline --full 2>/dev/null | python -c "
 import json,sys
 o=json.loads(sys.stdin.read())
 print(o['value'], o['ms_per_step'], o['parity_check']['max_abs_logit_err'])

@@ -2,7 +2,7 @@
 # models_vqa forward (bench.py --config 5) at 128 .. 1024 questions per launch, both recurrent-step modes
 for b in 128 256 512 1024; do
   for m in latency throughput; do
-    N2NMN_VQA_MODE=$m python bench.py --config 5 --batch $b --steps 20 --warmup 3 --no-cpu-baseline \
+    N2NMN_VQA_MODE=$m python bench.py --config 5 --batch $b --steps 20 --warmup 3 --no-cpu-baseline --full \
         2> gpurun_out/vq_${b}_$m.err | tail -1 > gpurun_out/vq_${b}_$m.json
     python - <<PY
 import json
