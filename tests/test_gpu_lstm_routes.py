@@ -1,0 +1,367 @@
+"""The recurrent step routes of the serving modes against the fp64 oracle at the 64-row block edges of
+lstm_tile_kernel and the 32-row tiles of the K-split kernel, with every intermediate the seq2seq half
+exposes (encoder outputs / h_transformed / final states, the teacher-forced decoder's outputs).
+
+Which kernel runs a pipelined two-layer encoder launch (csrc/capi.cpp encoder_impl; launch k runs
+layer-0 step k and layer-1 step k - 1):
+  * lstm_wide (capi.cpp:326): 'throughput' and 'throughput_bf16x3' ask for the tile kernels (2),
+    'throughput_ksplit' for the K-split tiles (1), 'latency' for neither (0);
+  * capi.cpp:516: with a host copy of the lengths (Engine.seq2seq passes one whenever seq_len is a
+    numpy array) a launch whose active-row count act[min(k, T - 1)] is <= tile_min_rows (default 192,
+    capi.cpp:345) takes the K-split tiles -- tile_min_rows 0 keeps the tile kernel at every step with
+    an active row, 1 << 30 never uses it; lengths handed over as a device tensor only leave the tile
+    kernel at every step;
+  * launch_lstm_step (csrc/kernels_seq2seq.hip:1601): wide >= 2 and N >= 128 -> lstm_tile_kernel<4, 0>
+    (kernels_lstm_tile.hip: row blocks past n_active are skipped, the ids behind them write the zero
+    output rows); wide == 1 -> lstm_step_wide_kernel<2> (32-row tiles); wide == 0 -> lstm_step_kernel<4, 0>;
+  * bf16x3 (capi.cpp:518-525): lstm_tile3 while wide == 2, the exact K-split tiles (which write the
+    bf16 planes of what they produce) once the count drops to tile_min_rows.
+The teacher-forced decoder (no eos_retire) takes lstm_wide's choice at every step (capi.cpp:718-727).
+
+Oracle: oracle/n2nmn_oracle.py encoder_forward / decoder_forward in float64.  Every question of the
+oracle is independent of the others, so it runs ONCE per length profile over a pool of questions; the
+batch of N rows of a profile is the first N pool columns in a shuffled order (the length sort `perm` is
+never the identity), and its oracle is the same columns of the pool's.
+
+Bars: encoder outputs, encoder_h_transformed and final states 2e-5 absolute (what test_gpu_bf16x3
+already asks of the split-operand mode); decoder outputs util.check_decoder's (1e-4; 2e-4 / 5e-4 for
+neg_entropy / log_seq_prob).  Past a question's length the encoder output and the attention are exactly
+0 (dynamic_rnn's zero output, nmn3_netgen_att.py:190-191).
+
+Baseline for later kernel work: the largest |diff| per route and tensor over all cases, on an MI355X.
+
+  route              enc_out  eht      c0       h0       c1       h1       tok_sc   atts     wvecs    tprobs   negent   lsp
+  tile               2.0e-7   4.2e-7   2.8e-7   1.8e-7   3.1e-7   2.0e-7   2.1e-7   9.8e-8   4.4e-8   1.8e-8   1.3e-5   1.2e-5
+  default            2.0e-7   4.2e-7   2.8e-7   1.8e-7   3.1e-7   2.0e-7   2.5e-7   9.8e-8   4.4e-8   1.8e-8   1.3e-5   1.3e-5
+  ksplit_tail        2.0e-7   4.0e-7   2.8e-7   1.6e-7   2.8e-7   1.8e-7   2.5e-7   1.1e-7   4.3e-8   1.8e-8   1.3e-5   1.3e-5
+  device_lens        2.0e-7   4.2e-7   2.8e-7   1.8e-7   3.1e-7   2.0e-7   2.1e-7   9.8e-8   4.4e-8   1.8e-8   1.3e-5   1.2e-5
+  throughput_ksplit  2.0e-7   4.0e-7   2.8e-7   1.6e-7   2.8e-7   1.8e-7   2.4e-7   9.9e-8   4.2e-8   1.8e-8   1.3e-5   1.3e-5
+  latency            2.0e-7   4.1e-7   2.8e-7   1.6e-7   2.9e-7   1.9e-7   2.1e-7   1.1e-7   4.3e-8   1.9e-8   1.3e-5   1.4e-5
+  bf16x3 (c, d, e)   1.8e-7   4.0e-7   2.4e-7   1.6e-7   2.8e-7   1.7e-7   2.2e-7   1.1e-7   3.9e-8   1.8e-8   1.3e-5   1.2e-5
+"""
+import numpy as np
+import pytest
+import torch
+
+from oracle import n2nmn_oracle as O
+from n2nmn_amd import synth
+from n2nmn_amd.spec import CLEVR_MODULE_NAMES, Dims, lstm_var
+from util import assert_close, check_decoder, maxdiff, t2n
+
+pytestmark = pytest.mark.gpu
+torch.set_num_threads(min(16, torch.get_num_threads()))     # the fp64 oracle's BLAS on a many-core host
+NAMES = list(CLEVR_MODULE_NAMES)
+CAP = 448                        # capacity of the engine: the largest batch below
+POOL = 257
+ENC_TOL = 2e-5
+NEVER = 1 << 30
+D = Dims()
+T = D.T_encoder
+
+
+def _profile_lengths(profile, n):
+    """(a) uniform in 1..T; (b) all T; (c) all 1; (d) column 0 T, the rest 1; (e) (n = 448) the active
+    count takes 257, 256, 193, 192, 191, 129, 128, 127, 65, 64, 63 at steps 10 .. 20 (every 64-row block
+    edge +- 1, and the default tile_min_rows 192 exactly)"""
+    if profile == 'b':
+        return np.full(n, T, np.int32)
+    if profile == 'c':
+        return np.ones(n, np.int32)
+    if profile == 'd':
+        lens = np.ones(n, np.int32)
+        lens[0] = T
+        return lens
+    assert profile == 'e' and n == CAP
+    rng = np.random.default_rng(5)
+    act = [257, 256, 193, 192, 191, 129, 128, 127, 65, 64, 63]      # act[t] = #{len > t}, t = 10 .. 20
+    lens = list(rng.integers(1, 11, size=n - act[0]))             # 191 rows of length <= 10
+    for t in range(len(act) - 1):
+        lens += [11 + t] * (act[t] - act[t + 1])                   # rows leaving after step 10 + t
+    lens += list(rng.integers(21, T + 1, size=act[-1] - 1)) + [T]  # 63 rows past step 20, one of length T
+    lens = np.array(lens, np.int32)
+    got = [(lens > t).sum() for t in range(10, 21)]
+    assert got == act, got
+    return lens
+
+
+_pools = {}
+
+
+def _pool(profile):
+    """(batch, gt, encoder oracle, decoder oracle) of the profile's question pool, computed once"""
+    if profile not in _pools:
+        n = CAP if profile == 'e' else POOL
+        seed = {'a': 41, 'b': 42, 'c': 43, 'd': 44, 'e': 45}[profile]
+        batch = synth.make_inputs(Dims(N=n), seed=seed, n=n, min_len=1)
+        batch.pop('image_feat_batch')
+        if profile != 'a':
+            lens = _profile_lengths(profile, n)
+            seq = batch['input_seq_batch']
+            seq[np.arange(T)[:, None] >= lens[None, :]] = 0
+            batch['seq_length_batch'] = lens
+        gt = synth.template_layout_batch(D, n=n, offset=seed)
+        enc = O.encoder_forward(W, batch['input_seq_batch'], batch['seq_length_batch'], np.float64)
+        P, Wv, bv = O.build_validity_mats(NAMES)
+        dec = O.decoder_forward(W, enc, P, Wv, bv, D.T_decoder, np.float64, use_gt_layout=True, gt_layout=gt)
+        _pools[profile] = (batch, gt, enc, dec)
+    return _pools[profile]
+
+
+def _take_enc(enc, cols):
+    return dict(outputs=enc['outputs'][:, cols], h_transformed=enc['h_transformed'][:, cols],
+                states=tuple((c[cols], h[cols]) for c, h in enc['states']))
+
+
+def _take_dec(dec, cols):
+    return dict(token_scores=dec['token_scores'][:, cols], atts=dec['atts'][:, :, cols],
+                word_vecs=dec['word_vecs'][:, cols], token_probs=dec['token_probs'][:, cols],
+                neg_entropy=dec['neg_entropy'][cols])
+
+
+def _case(profile, n):
+    """the N-row batch of a profile: pool columns 0 .. n - 1 in a shuffled order, with its oracle"""
+    batch, gt, enc, dec = _pool(profile)
+    cols = np.random.default_rng(1000 + n).permutation(n)
+    assert (cols != np.arange(n)).any()
+    b = dict(input_seq_batch=np.ascontiguousarray(batch['input_seq_batch'][:, cols]),
+             seq_length_batch=np.ascontiguousarray(batch['seq_length_batch'][cols]))
+    return b, np.ascontiguousarray(gt[:, cols]), _take_enc(enc, cols), _take_dec(dec, cols)
+
+
+W = synth.make_weights(D, seed=0)
+
+
+@pytest.fixture(scope='module')
+def eng():
+    from n2nmn_amd.engine import Engine
+    from n2nmn_amd.nmn3_assembler import Assembler
+    e = Engine(Dims(N=CAP), Assembler(NAMES))
+    e.load_weights(W)
+    return e
+
+
+# route id -> (mode, tile_min_rows switch or None, host copy of the lengths)
+ROUTES = {
+    'tile': ('throughput', 0, True),
+    'default': ('throughput', None, True),
+    'ksplit_tail': ('throughput', NEVER, True),
+    'device_lens': ('throughput', None, False),
+    'throughput_ksplit': ('throughput_ksplit', None, True),
+    'latency': ('latency', None, True),
+    'bf16x3': ('throughput_bf16x3', None, True),
+}
+
+
+def _run(eng, route, batch, gt, **kw):
+    mode, tmr, host = ROUTES[route]
+    lens = batch['seq_length_batch']
+    if not host:
+        lens = torch.as_tensor(lens, device=eng.device)
+    eng.set_mode(mode)
+    try:
+        if tmr is not None:
+            eng.debug_set('tile_min_rows', tmr)
+        out = eng.seq2seq(batch['input_seq_batch'], lens, use_gt_layout=True, gt_layout=gt, **kw)
+        torch.cuda.synchronize()
+        return {k: t2n(v).copy() for k, v in out.items() if not k.startswith('_')}
+    finally:
+        eng.debug_set('tile_min_rows', None)
+        eng.set_mode('latency')
+
+
+def _check_all(out, batch, enc, dec):
+    """every intermediate against the oracle; returns the max |diff| per tensor"""
+    lens = batch['seq_length_batch']
+    diffs = {'encoder_outputs': assert_close('encoder_outputs', out['encoder_outputs'], enc['outputs'], ENC_TOL),
+             'encoder_h_transformed': assert_close('encoder_h_transformed', out['encoder_h_transformed'],
+                                                   enc['h_transformed'], ENC_TOL)}
+    past = np.arange(T)[:, None] >= lens[None, :]                     # [T, N]
+    assert np.all(out['encoder_outputs'][past] == 0.0), 'encoder output past a length is not exactly 0'
+    for l in range(2):
+        diffs['c%d' % l] = assert_close('c%d' % l, out['encoder_states'][l, 0], enc['states'][l][0], ENC_TOL)
+        diffs['h%d' % l] = assert_close('h%d' % l, out['encoder_states'][l, 1], enc['states'][l][1], ENC_TOL)
+    diffs.update(check_decoder(out, dec))
+    assert np.all(out['atts'][:, past] == 0.0), 'attention past a length is not exactly 0'
+    return diffs
+
+
+CASES = [(p, n) for p in 'abcd' for n in (129, 200, 256, 257)] + [('e', CAP)]
+EXACT_ROUTES = ['tile', 'default', 'ksplit_tail', 'device_lens', 'throughput_ksplit', 'latency']
+ROUTE_CASES = [(r, p, n) for p, n in CASES for r in EXACT_ROUTES] + \
+              [('bf16x3', p, n) for p, n in CASES if p in 'cde']
+
+
+@pytest.mark.parametrize('route,profile,n', ROUTE_CASES, ids=['%s-%s%d' % c for c in ROUTE_CASES])
+def test_route_matches_the_oracle(eng, route, profile, n):
+    batch, gt, enc, dec = _case(profile, n)
+    out = _run(eng, route, batch, gt, debug=True)
+    assert np.array_equal(out['predicted_tokens'], gt)
+    diffs = _check_all(out, batch, enc, dec)
+    print('\nROUTE %-17s %s%-4d %s' % (route, profile, n, ' '.join('%s=%.2e' % kv for kv in diffs.items())))
+
+
+PER_ROW = {'encoder_outputs': 1, 'encoder_h_transformed': 1, 'encoder_states': 2, 'token_scores': 1,
+           'atts': 2, 'word_vecs': 1, 'token_probs': 1, 'neg_entropy': 0, 'log_seq_prob': 0,
+           'predicted_tokens': 1}                           # axis of the batch row in each output
+
+
+def _same_bits(name, a, b):
+    assert a.shape == b.shape, name
+    bad = a.view(np.uint32) != b.view(np.uint32) if a.dtype == np.float32 else a != b
+    assert not bad.any(), '%s: %d entries differ in their bits (max |diff| %.3e)' % (
+        name, int(bad.sum()), maxdiff(a, b))
+
+
+@pytest.mark.parametrize('route', ['tile', 'ksplit_tail'])
+@pytest.mark.parametrize('profile,n', [('a', 257), ('e', CAP)])
+def test_column_permutation_permutes_every_output_bit_for_bit(eng, route, profile, n):
+    """Each row's dot products run in a fixed k order wherever the row sits in the length-sorted state
+    (the MFMA tile position, the row block, the 32-row K-split tile), so a permuted batch must give the
+    permuted outputs exactly: a wrong `perm` index or a stale state in a skipped block does not hide
+    behind a tolerance here."""
+    batch, gt, _, _ = _case(profile, n)
+    p = np.random.default_rng(7).permutation(n)
+    pb = dict(input_seq_batch=np.ascontiguousarray(batch['input_seq_batch'][:, p]),
+              seq_length_batch=np.ascontiguousarray(batch['seq_length_batch'][p]))
+    ref = _run(eng, route, batch, gt, debug=True)
+    out = _run(eng, route, pb, np.ascontiguousarray(gt[:, p]), debug=True)
+    for k, ax in PER_ROW.items():
+        _same_bits(k, out[k], np.take(ref[k], p, axis=ax))
+
+
+@pytest.mark.parametrize('route', ['tile', 'ksplit_tail'])
+def test_a_question_does_not_depend_on_its_neighbours(eng, route):
+    """64 fixed questions inside a 256-row batch of profile (a) and inside one of profile (d), at
+    different columns: their outputs agree bit for bit (the batches differ in which row blocks are
+    skipped, zero-filled and handed to the K-split tiles at which step)."""
+    pa, ga, _, _ = _pool('a')
+    pd, gd, _, _ = _pool('d')
+    rng = np.random.default_rng(9)
+    q = np.arange(193, 257)                                 # the fixed questions: pool (a) columns
+    outs = []
+    for pool, gpool, others in ((pa, ga, np.arange(192)), (pd, gd, np.arange(192))):
+        pos = np.sort(rng.choice(256, size=64, replace=False))
+        rest = np.setdiff1d(np.arange(256), pos)
+        seq = np.zeros((T, 256), np.int32)
+        lens = np.zeros(256, np.int32)
+        gt = np.zeros((D.T_decoder, 256), np.int32)
+        seq[:, pos], lens[pos], gt[:, pos] = pa['input_seq_batch'][:, q], pa['seq_length_batch'][q], ga[:, q]
+        seq[:, rest] = pool['input_seq_batch'][:, others]
+        lens[rest] = pool['seq_length_batch'][others]
+        gt[:, rest] = gpool[:, others]
+        out = _run(eng, route, dict(input_seq_batch=seq, seq_length_batch=lens), gt, debug=True)
+        outs.append({k: np.take(out[k], pos, axis=ax) for k, ax in PER_ROW.items()})
+    for k in PER_ROW:
+        _same_bits(k, outs[1][k], outs[0][k])
+
+
+def test_tile_to_ksplit_handover_step(eng):
+    """Profile (e) has act[12] = 193 and act[13] = 192 rows: with the default tile_min_rows (192) launches
+    0 .. 12 run lstm_tile_kernel and launches 13 .. T the K-split tiles (capi.cpp:516).  Layer-1 step t runs
+    in launch t + 1, so the encoder outputs of steps 0 .. 11 carry the tile kernel's bits (those of the
+    all-tile route) and step 12 is the K-split kernel's first, which rounds differently.  Both kernels are
+    exact fp32, so a handover one step early or late passes every tolerance: only the bits pin it."""
+    batch, gt, _, _ = _case('e', CAP)
+    assert [(batch['seq_length_batch'] > t).sum() for t in (12, 13)] == [193, 192]
+    tile = _run(eng, 'tile', batch, gt, debug=True)['encoder_outputs']
+    dflt = _run(eng, 'default', batch, gt, debug=True)['encoder_outputs']
+    _same_bits('encoder outputs of steps 0 .. 11', dflt[:12], tile[:12])
+    assert (dflt[12].view(np.uint32) != tile[12].view(np.uint32)).any(), \
+        'step 12 has the tile kernel\'s bits: the K-split tiles did not take over at launch 13'
+
+
+@pytest.mark.parametrize('profile', ['a', 'd'])
+def test_encoder_h_transform_over_listed_rows(eng, profile):
+    """eht_rows (capi.cpp:411): when the encoder_h_transform GEMM is deferred into the decoder's GEMM
+    launch -- every pass that does not fetch encoder_h_transformed (capi.cpp:1723) -- and T * N >= 8192, it
+    runs over the rows inside their question's length only and the attention takes the bias for the others
+    (a debug fetch of encoder_h_transformed refuses the partial matrix, capi.cpp:559, so the pass runs
+    without debug outputs).  Both settings match the oracle and each other.  The profile counters pin that
+    the listed-row form really ran: with the host lengths known, the deferred launch counts the GEMM over
+    sum(len) rows instead of T * N (capi.cpp:541-545, 742), nothing else differs between the passes."""
+    batch, gt, _, dec = _case(profile, 256)
+    L = D.lstm_dim
+    got, flops = {}, {}
+    for on in (1, 0):
+        eng.debug_set('eht_rows', on)
+        try:
+            eng.profile_begin()
+            got[on] = _run(eng, 'default', batch, gt)
+            flops[on] = sum(f['flops'] for f in eng.profile_end())
+        finally:
+            eng.debug_set('eht_rows', None)
+        assert 'encoder_h_transformed' not in got[on]
+        assert_close('atts (eht_rows=%d)' % on, got[on]['atts'], dec['atts'][..., 0], 1e-4)
+        assert_close('token_probs (eht_rows=%d)' % on, got[on]['token_probs'], dec['token_probs'], 1e-4)
+        assert_close('word_vecs (eht_rows=%d)' % on, got[on]['word_vecs'], dec['word_vecs'], 1e-4)
+    for k in ('atts', 'token_probs', 'word_vecs'):
+        assert_close(k + ': eht_rows 1 vs 0', got[1][k], got[0][k], 1e-6)
+    skipped = T * 256 - int(batch['seq_length_batch'].sum())
+    assert skipped > 0
+    want = 2.0 * skipped * L * L
+    assert abs((flops[0] - flops[1]) - want) <= 1e-9 * flops[0], \
+        'eht_rows=1 did not run the listed-row GEMM: counted flops differ by %.6e, want %.6e' % (
+            flops[0] - flops[1], want)
+
+
+def _saturated_weights():
+    """Input rows of every LSTM weight matrix (x . W_x, and h0 . W for layer 1) x 8, word embeddings x 32:
+    the gate pre-activations of encoder layer 0 reach ~44, of layer 1 ~10, and fast_sigmoid / fast_tanh
+    (csrc/device_utils.h, exp2 + rcp) work at their extremes, as with trained weights.  The recurrent
+    rows keep their scale: with them x 8 as well (and the embeddings x 4) the 45-step recurrence
+    amplifies rounding about 10^4-fold -- an fp32 evaluation with exact transcendentals (the oracle in
+    float32) lands 3.2e-3 from the fp64 one, fp64 with 1e-7 relative noise on one weight matrix 1e-4 --
+    so no fp32 kernel can be held to 2e-5 there (the tile and K-split routes landed at 2.1e-3 and
+    2.9e-3).  Here the float32 oracle stays within 6e-6 of the fp64 one."""
+    L = D.lstm_dim
+    w = dict(W)
+    for part in ('encoder', 'decoder'):
+        for layer in range(2):
+            k = lstm_var(part, layer, 'weights')
+            m = W[k].copy()
+            m[:m.shape[0] - L] *= np.float32(8)
+            w[k] = m
+    for k in list(w):
+        if k.endswith('embedding_mat') or k.endswith('go_embedding'):
+            w[k] = W[k] * np.float32(32)
+    return w
+
+
+@pytest.mark.parametrize('route', ['tile', 'ksplit_tail'])
+def test_saturated_gates(eng, route):
+    """bars: h and the encoder outputs 2e-5 absolute, c 2e-5 * max(1, |c|), the decoder util.check_decoder's,
+    everything finite"""
+    batch, gt, _, _ = _case('a', 256)
+    ws = _saturated_weights()
+    if 'sat' not in _pools:
+        # the oracle's cells report how far the gates are driven
+        cell, zmax = O._lstm_cell, [0.0]
+
+        def spy(x, c, h, Wm, bm):
+            zmax[0] = max(zmax[0], float(np.abs(np.concatenate([x, h], axis=1) @ Wm + bm).max()))
+            return cell(x, c, h, Wm, bm)
+        with pytest.MonkeyPatch.context() as mp:
+            mp.setattr(O, '_lstm_cell', spy)
+            enc = O.encoder_forward(ws, batch['input_seq_batch'], batch['seq_length_batch'], np.float64)
+        P, Wv, bv = O.build_validity_mats(NAMES)
+        dec = O.decoder_forward(ws, enc, P, Wv, bv, D.T_decoder, np.float64, use_gt_layout=True, gt_layout=gt)
+        _pools['sat'] = enc, dec, zmax[0]
+    enc, dec, zmax = _pools['sat']
+    assert zmax > 30, zmax
+    eng.load_weights(ws)
+    try:
+        out = _run(eng, route, batch, gt, debug=True)
+    finally:
+        eng.load_weights(W)
+    for k in ('encoder_outputs', 'encoder_states', 'token_scores', 'atts', 'word_vecs', 'token_probs',
+              'neg_entropy', 'log_seq_prob'):
+        assert np.isfinite(out[k]).all(), k
+    diffs = {'encoder_outputs': assert_close('encoder_outputs', out['encoder_outputs'], enc['outputs'], ENC_TOL)}
+    for l in range(2):
+        c_ref, h_ref = enc['states'][l]
+        diffs['h%d' % l] = assert_close('h%d' % l, out['encoder_states'][l, 1], h_ref, ENC_TOL)
+        rel = np.abs(out['encoder_states'][l, 0] - c_ref) / np.maximum(1.0, np.abs(c_ref))
+        assert rel.max() <= ENC_TOL, 'c%d: max |diff| / max(1, |c|) = %.3e' % (l, rel.max())
+        diffs['c%d_rel' % l] = float(rel.max())
+    diffs.update(check_decoder(out, dec))
+    print('\nSATURATED %-11s max |z| %.1f %s' % (route, zmax, ' '.join('%s=%.2e' % kv for kv in diffs.items())))

@@ -7,7 +7,7 @@ import pytest
 
 from oracle import n2nmn_oracle as O
 from n2nmn_amd import synth
-from util import assert_close, t2n
+from util import assert_close, check_decoder, t2n
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -37,16 +37,6 @@ def test_encoder(clevr_engine, n, seed):
         assert_close('h%d' % l, st[l, 1], enc['states'][l][1], TOL)
 
 
-def _check_decoder(out, dec, d, check_tokens_margin=True):
-    assert_close('token_scores', t2n(out['token_scores']), dec['token_scores'], TOL)
-    assert_close('atts', t2n(out['atts']), dec['atts'][..., 0], TOL)
-    assert_close('word_vecs', t2n(out['word_vecs']), dec['word_vecs'], TOL)
-    assert_close('token_probs', t2n(out['token_probs']), dec['token_probs'], TOL)
-    assert_close('neg_entropy', t2n(out['neg_entropy']), dec['neg_entropy'], 2e-4)
-    lsp = np.sum(np.log(dec['token_probs']), axis=0)
-    assert_close('log_seq_prob', t2n(out['log_seq_prob']), lsp, 5e-4)
-
-
 @pytest.mark.parametrize('n,seed', [(64, 0), (6, 4)])
 def test_decoder_greedy(clevr_engine, n, seed):
     eng, d, asm, w = clevr_engine
@@ -72,7 +62,7 @@ def test_decoder_greedy(clevr_engine, n, seed):
     out = eng.seq2seq(batch['input_seq_batch'], batch['seq_length_batch'], debug=True,
                       forced_tokens=dec['predicted_tokens'])
     assert np.array_equal(t2n(out['predicted_tokens']), dec['predicted_tokens'])
-    _check_decoder(out, dec, d)
+    check_decoder(out, dec)
 
 
 def test_decoder_teacher_forcing(clevr_engine):
@@ -90,7 +80,7 @@ def test_decoder_teacher_forcing(clevr_engine):
     out = eng.seq2seq(batch['input_seq_batch'], batch['seq_length_batch'], T_dec=T,
                       use_gt_layout=True, gt_layout=gt, debug=True)
     assert np.array_equal(t2n(out['predicted_tokens']), gt)
-    _check_decoder(out, dec, d10)
+    check_decoder(out, dec)
 
 
 def test_decoder_sampling(clevr_engine):
@@ -114,7 +104,7 @@ def test_decoder_sampling(clevr_engine):
     assert len(np.unique(tok[0])) >= 2          # it actually samples
     out = eng.seq2seq(batch['input_seq_batch'], batch['seq_length_batch'], sample_uniforms=uni,
                       forced_tokens=dec['predicted_tokens'], debug=True)
-    _check_decoder(out, dec, d)
+    check_decoder(out, dec)
 
 
 def test_short_shapes(clevr_engine):
@@ -127,7 +117,7 @@ def test_short_shapes(clevr_engine):
     dec = O.decoder_forward(w, enc, asm.P, asm.W, asm.b, 6, np.float64)
     out = eng.seq2seq(batch['input_seq_batch'], batch['seq_length_batch'], T_dec=6, debug=True,
                       forced_tokens=dec['predicted_tokens'])
-    _check_decoder(out, dec, ds)
+    check_decoder(out, dec)
 
 
 def test_capacity_and_argument_errors(clevr_engine):
@@ -163,7 +153,7 @@ def test_throughput_mode_tiles(clevr_engine, n, seed):
         P, Wv, bv = O.build_validity_mats(list(asm.module_names))
         dec = O.decoder_forward(w, enc, P, Wv, bv, d.T_decoder, np.float64, use_gt_layout=True,
                                 gt_layout=gt)
-        _check_decoder(out, dec, d)
+        check_decoder(out, dec)
     finally:
         eng.set_mode('latency')
     from n2nmn_amd import _lib
@@ -187,7 +177,7 @@ def test_sequential_decoder_attention_at_wave_boundaries(clevr_engine):
     dec = O.decoder_forward(w, enc, asm.P, asm.W, asm.b, d.T_decoder, np.float64)
     out = eng.seq2seq(batch['input_seq_batch'], batch['seq_length_batch'], debug=True,
                       forced_tokens=dec['predicted_tokens'])
-    _check_decoder(out, dec, d)
+    check_decoder(out, dec)
     atts = t2n(out['atts'])                                      # [T_dec, T_enc, N]
     past = np.arange(T)[None, :, None] >= lens[None, None, :]
     assert np.all(atts[np.broadcast_to(past, atts.shape)] == 0.0)

@@ -120,14 +120,9 @@ def _token_validity(asm, tokens, T_dec):
     return out
 
 
-def test_vqa_policy_gradient_step_with_dropout_matches_oracle(setup):
-    """exp_vqa/train_vqa_rl_gt_layout.py:106-126: the layout is sampled from the network under this
-    step's dropout masks, then REINFORCE + entropy + answer loss through the same masks.  Oracle:
-    loss_and_grads_rl(vqa_masks=...) on the tokens the GPU sampled (its CLEVR form is pinned to the
-    reference's RL loss block, its models_vqa + dropout forward to the vqa_train fixture)."""
+def _check_rl_step_with_dropout(d, batch, eng, tr, w):
     from oracle import n2nmn_oracle as O
     from oracle import n2nmn_oracle_grad as G
-    d, batch, gt, eng, tr, w = setup
     eng.load_weights(w)
     masks = FC.vqa_dropout_masks(d)
     tr.baseline.fill_(1.25)
@@ -155,3 +150,33 @@ def test_vqa_policy_gradient_step_with_dropout_matches_oracle(setup):
         if not err <= tol:
             bad.append('%s: %.3e > %.3e' % (k, err, tol))
     assert not bad, '\n'.join(bad)
+
+
+def test_vqa_policy_gradient_step_with_dropout_matches_oracle(setup):
+    """exp_vqa/train_vqa_rl_gt_layout.py:106-126: the layout is sampled from the network under this
+    step's dropout masks, then REINFORCE + entropy + answer loss through the same masks.  Oracle:
+    loss_and_grads_rl(vqa_masks=...) on the tokens the GPU sampled (its CLEVR form is pinned to the
+    reference's RL loss block, its models_vqa + dropout forward to the vqa_train fixture)."""
+    d, batch, gt, eng, tr, w = setup
+    _check_rl_step_with_dropout(d, batch, eng, tr, w)
+
+
+def test_vqa_policy_gradient_step_with_dropout_at_130_rows_in_throughput_mode():
+    """The same step and bars at 130 rows in 'throughput' mode: the recurrent steps of the training forward
+    run on lstm_tile_kernel (>= 128 rows, lstm_dim 1000 padded to 1024) with its dropout epilogue -- the
+    dropped copy of layer 0's output for layer 1 and its saved copy for the backward (h_drop / save_hd) --
+    over two full 64-row blocks and a last block of 2 rows; the backward runs over the same ragged blocks."""
+    from n2nmn_amd.vqa import VQADims, VQAEngine, VQATrainer
+    c = FC.VQA_CASE
+    d = VQADims(N=130, T_encoder=c['T_enc'], T_decoder=c['T_dec'])
+    rng = np.random.default_rng(130)
+    lens = rng.integers(1, d.T_encoder + 1, size=d.N).astype(np.int32)
+    seq = rng.integers(0, d.num_vocab_txt, size=(d.T_encoder, d.N)).astype(np.int32)
+    seq[np.arange(d.T_encoder)[:, None] >= lens[None, :]] = 0
+    feat = np.maximum(rng.standard_normal((d.N, d.H, d.W, d.D)), 0).astype(np.float32)
+    batch = dict(input_seq_batch=seq, seq_length_batch=lens, image_feat_batch=feat,
+                 answer_label_batch=FC.vqa_labels(d))
+    eng = VQAEngine(d)
+    w = FC.vqa_weights(d)
+    eng.engine.set_mode('throughput')
+    _check_rl_step_with_dropout(d, batch, eng, VQATrainer(eng), w)

@@ -18,6 +18,22 @@ def t2n(t):
     return t.detach().cpu().numpy()
 
 
+def check_decoder(out, dec, tol=1e-4):
+    """Decoder outputs of Engine.seq2seq(debug=True) against an oracle decoder run on the same tokens
+    (SURVEY.md 8(c)): token_scores / atts / word_vecs / token_probs within `tol`, neg_entropy within
+    2e-4, log_seq_prob within 5e-4 (device tensors or host arrays).  Returns the max |diff| per tensor."""
+    got = {k: t2n(v) if hasattr(v, 'detach') else v for k, v in out.items()}
+    lsp = np.sum(np.log(dec['token_probs']), axis=0)
+    return {
+        'token_scores': assert_close('token_scores', got['token_scores'], dec['token_scores'], tol),
+        'atts': assert_close('atts', got['atts'], dec['atts'][..., 0], tol),
+        'word_vecs': assert_close('word_vecs', got['word_vecs'], dec['word_vecs'], tol),
+        'token_probs': assert_close('token_probs', got['token_probs'], dec['token_probs'], tol),
+        'neg_entropy': assert_close('neg_entropy', got['neg_entropy'], dec['neg_entropy'], 2e-4),
+        'log_seq_prob': assert_close('log_seq_prob', got['log_seq_prob'], lsp, 5e-4),
+    }
+
+
 def greedy_tokens_under_margin_rule(tokens, ref_dec, what='', margin_tol=1e-3):
     """free-running decoder tokens [T, n] against an oracle / reference decoder run on
     the same questions (`ref_dec` = dict with predicted_tokens [T, n], token_scores [T, n, V],
