@@ -480,7 +480,13 @@ typedef struct {
    *                + weight_decay * l2_reg;   baseline += (1 - baseline_decay)(avg - baseline)
    * gt_layout then holds the tokens the decoder SAMPLED for this batch (n2nmn_seq2seq_forward
    * with sample_uniforms); token validity comes from the automaton as it did when they were drawn
-   * (nmn3_netgen_att.py:200-260), `p` is the program assembled from them.                   */
+   * (nmn3_netgen_att.py:200-260), `p` is the program assembled from them.  N2NMN_VARIANT_SHAPES
+   * takes this objective too (exp_shapes/train_shapes_scratch.py:142-161; no automaton: every
+   * token valid, <eos> latch as in its cloning loss).
+   * N2NMN_OBJ_POLICY_GRADIENT_SAMPLED (N2NMN_VARIANT_SHAPES) is the same loss on the layouts
+   * n2nmn_train_sample drew inside THIS step: gt_layout = its tokens_out, `p` the program
+   * assembled from them, expr_validity the assembler's; n2nmn_train_forward then runs the module
+   * network and the loss only.                                                               */
   int32_t objective;
   const int32_t *expr_validity;    /* [N] device: 1 = the layout assembled (n2nmn_assemble)  */
   float invalid_expr_loss;         /* 0.5           (train_clevr_rl_gt_layout.py:40)         */
@@ -503,6 +509,7 @@ typedef struct {
 } n2nmn_train_io;
 #define N2NMN_OBJ_CLONING 0
 #define N2NMN_OBJ_POLICY_GRADIENT 1
+#define N2NMN_OBJ_POLICY_GRADIENT_SAMPLED 2
 
 /* Allocates the training workspace of a ROOT context (saved activations, backward scratch, Adam
  * moments: ~0.5 GB at CLEVR dimensions).  Idempotent. */
@@ -514,6 +521,18 @@ int n2nmn_grad_layout(const n2nmn_ctx *ctx, int variable, int64_t *offset, int64
  * keeps every activation the backward pass needs inside the context */
 int n2nmn_train_forward(n2nmn_ctx *ctx, const n2nmn_train_io *io, n2nmn_program *p,
                         n2nmn_stream stream);
+/* Sampling phase of a models_shapes training step (exp_shapes/train_shapes_scratch.py:204-216, part 1 of its
+ * partial_run): shapes_convnet, the encoder, and the decoder SAMPLING a layout per question under
+ * io->drop_enc0 / drop_dec0, with every activation the backward pass needs kept -- the reference samples
+ * inside the training graph, once.  Reads io->input_seq, seq_length, T_enc, N, T_dec, image_feat and the two
+ * dropout pointers.  sample_uniforms [T_dec, N] in [0, 1) replace tf.multinomial's generator (the
+ * inverse-CDF rule of n2nmn_seq2seq_forward).  tokens_out [T_dec, N] (device) receives the tokens under the
+ * <eos> latch of models_shapes/nmn3_netgen_att.py:210-226: behind a row's first <eos> the token is <eos>, its
+ * probability 1, its entropy 0, and the <eos> embedding feeds the next step.  The step continues with
+ * n2nmn_train_forward (objective N2NMN_OBJ_POLICY_GRADIENT_SAMPLED, same N / T_enc / T_dec, no weight
+ * change in between; otherwise N2NMN_EINVAL) and n2nmn_train_backward. */
+int n2nmn_train_sample(n2nmn_ctx *ctx, const n2nmn_train_io *io, const float *sample_uniforms,
+                       int32_t *tokens_out, n2nmn_stream stream);
 /* phase 0: module network + decoder (zeroes io->grads first); phase 1: encoder.  Must follow
  * n2nmn_train_forward with the same io / program, in this order, on the same stream.
  * The weight-gradient GEMMs are leaves of the backward graph and run on a library-owned side stream
@@ -547,7 +566,7 @@ int n2nmn_train_reset_optimizer(n2nmn_ctx *ctx, n2nmn_stream stream);
 int n2nmn_get_weight(n2nmn_ctx *ctx, const char *name, float *out, n2nmn_stream stream);
 /* debug / parity: copy an internal gradient tensor ("d_word_vecs" [T_dec,N,E], "d_token_scores"
  * [T_dec,N,16], "d_encoder_outputs" [T_enc,N,L], "d_encoder_h_transformed" [T_enc,N,L],
- * "d_scores" [N,C], "token_scores" [T_dec,N,V] (the forward's token logits), N2NMN_VARIANT_SHAPES: "d_image_feat" [N,H,W,D], the gradient arriving at
+ * "d_scores" [N,C], "token_scores" [T_dec,N,V] (the forward's token logits), "log_seq_prob" [N], N2NMN_VARIANT_SHAPES: "d_image_feat" [N,H,W,D], the gradient arriving at
  * shapes_convnet's output) into `out` (device, capacity in floats); returns the element count */
 int64_t n2nmn_train_debug_tensor(n2nmn_ctx *ctx, const char *name, float *out, int64_t capacity,
                                  n2nmn_stream stream);

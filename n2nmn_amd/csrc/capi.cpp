@@ -833,6 +833,11 @@ int decoder_impl(n2nmn_ctx* c, const n2nmn_seq2seq_io* io, hipStream_t s, const 
       launch_gemm_pkn(list, nl, s);
     }
     launch_dec_init(c->state, N, Td, s);
+    // A recorded pass (the sampling phase of a training step, n2nmn_train_sample) keeps per step what the
+    // teacher-forced pass keeps: gates / cell / hidden states, q, the top-layer h, context, logits, validity
+    const size_t rnl = (size_t)N * L;
+    const bool latch = c->rec && c->rec->eos_seen;     // models_shapes: <eos> latch on the sampled tokens
+    if (latch) N2_HIP(hipMemsetAsync(c->rec->eos_seen, 0, sizeof(int32_t) * N, s));
     // ---- eos_retire for sequential decoding: a row that has emitted <eos> leaves the recurrence.  After
     // every step dec_compact_kernel re-partitions the state rows (live ones in front, gathered into the
     // alternate state buffers) and the launches of the next step run over that dense prefix; the host
@@ -874,6 +879,11 @@ int decoder_impl(n2nmn_ctx* c, const n2nmn_seq2seq_io* io, hipStream_t s, const 
       j0.perm = live_perm; j0.n_active = live_n;
       if (io->drop_dec0) {             // sampling from the network with dropout (policy gradient)
         j0.drop = io->drop_dec0 + (size_t)t * N * L; j0.h_drop = c->dhd[t & 1];
+        j0.save_hd = c->rec ? c->rec->dh0d + t * rnl : nullptr;
+      }
+      if (c->rec) {
+        j0.save_gates = c->rec->dg0 + t * rnl; j0.save_c = c->rec->dc0s + (t + 1) * rnl;
+        j0.save_h = c->rec->dh0s + (t + 1) * rnl;
       }
       {
         ProfScope ps(c, F_LSTM_DEC0, fl0 * live / N, 4.0 * ((double)L * 4 * L + 3.0 * live * L), s);
@@ -890,7 +900,12 @@ int decoder_impl(n2nmn_ctx* c, const n2nmn_seq2seq_io* io, hipStream_t s, const 
       LstmJob j1{};
       j1.active = 1;
       packed_state(c, j1);
-      j1.out_seq = c->dh1_rm;          // row-major copy of the top-layer h for dec_attn (by ORIGINAL row)
+      // row-major copy of the top-layer h for dec_attn (by ORIGINAL row); a recorded pass keeps every step's
+      j1.out_seq = c->rec ? c->dec_h1_all + t * rnl : c->dh1_rm;
+      if (c->rec) {
+        j1.save_gates = c->rec->dg1 + t * rnl; j1.save_c = c->rec->dc1s + (t + 1) * rnl;
+        j1.save_h = c->rec->dh1s + (t + 1) * rnl;
+      }
       j1.A0 = io->drop_dec0 ? c->dhd[t & 1] : hb0[h0w];
       j1.A1 = t == 0 ? c->fh1 : hb1[h1w ^ 1]; j1.K = 2 * L;
       j1.Wp = c->dec_W1_t; j1.Wp64 = c->dec_W1_64; j1.ntiles = L / 4; j1.bias = c->dec_b1_t;
@@ -911,12 +926,13 @@ int decoder_impl(n2nmn_ctx* c, const n2nmn_seq2seq_io* io, hipStream_t s, const 
       packed_state(c, jq);
       jq.hp_R = 0;
       jq.active = 1; jq.mode = 1; jq.A0 = hb1[h1w]; jq.K = L; jq.Wp = c->att_W_t;     // (q in STATE-row order)
-      jq.ntiles = L / 16; jq.bias = c->vars[V_ATT_B].mirror; jq.h_new = c->qbuf; jq.ldo = L;
+      jq.ntiles = L / 16; jq.bias = c->vars[V_ATT_B].mirror; jq.ldo = L;
+      jq.h_new = c->rec ? c->qbuf + t * rnl : c->qbuf;
       {
         ProfScope ps(c, F_LINEAR_Q, 2.0 * N * L * L, 4.0 * ((double)L * L + 2.0 * N * L), s);
         launch_lstm_step(&jq, 1, N, L, 32, s);
       }
-      a.q = c->qbuf; a.out = c->dh1_rm;
+      a.q = jq.h_new; a.out = j1.out_seq;
       a.gt = io->gt_layout ? io->gt_layout + (size_t)t * N : nullptr;
       a.uni = io->sample_uniforms ? io->sample_uniforms + (size_t)t * N : nullptr;
       a.forced = io->forced_tokens ? io->forced_tokens + (size_t)t * N : nullptr;
@@ -925,6 +941,12 @@ int decoder_impl(n2nmn_ctx* c, const n2nmn_seq2seq_io* io, hipStream_t s, const 
       a.scores = io->token_scores ? io->token_scores + (size_t)t * N * V : nullptr;
       a.next_idx = c->next_idx;
       a.live_perm = live_perm; a.live_n = live_n; a.eos_token = root(c)->eos_token;
+      if (c->rec) {
+        a.ctx_out = c->rec->ctx + t * rnl;
+        if (!a.scores) a.scores = c->rec->tscores + (size_t)t * N * V;
+        a.valid_bits = c->rec->valid_bits + (size_t)t * N;
+      }
+      if (latch) { a.eos_seen = c->rec->eos_seen; a.latch_eos = V - 1; }
       {
         ProfScope ps(c, F_DEC_STEP, att_fl * live / N, att_by * live / N, s);
         launch_dec_attn(a, 1, s);

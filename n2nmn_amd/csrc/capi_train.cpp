@@ -78,6 +78,7 @@ struct TrainState {
   int64_t total = 0, split = 0;
   int KpL4 = 0;                       // round_up(4L, 32)
   int last_N = 0, last_T = 0, last_Td = 0;   // shape of the forward currently held
+  bool sampled = false;               // ... and it is a sampling pass (n2nmn_train_sample) awaiting its module network
   // Weight-gradient GEMMs are leaves of the backward graph: they run on a low-priority side
   // stream while the latency-bound chains (BPTT, attention backward) continue on the caller's.
   hipStream_t side = nullptr;
@@ -183,6 +184,7 @@ size_t carve_train(n2nmn_ctx* c, TrainState* t, char* base) {
   t->dscores = k.take<float>(N * C + 4);
   t->rl_coef = k.take<float>(N);
   r.valid_bits = k.take<int32_t>(Td * N);
+  if (shapes) r.eos_seen = k.take<int32_t>(N);
   t->dsc = k.take<float>(Td * N * 16);
   // [zero block: cleared by ONE memset at the start of backward phase 0]
   t->zero_begin = reinterpret_cast<char*>(k.take<float>(0));
@@ -590,9 +592,12 @@ static int check_train_io(const n2nmn_ctx* c, const n2nmn_train_io* io, const n2
              N2NMN_ECAPACITY, std::string(what) + ": N / T_enc / T_dec exceed the context capacity");
   N2_REQUIRE(p->prog.num_rows == io->N, N2NMN_EINVAL,
              std::string(what) + ": program was not assembled from this batch");
-  N2_REQUIRE(io->objective == N2NMN_OBJ_CLONING || io->objective == N2NMN_OBJ_POLICY_GRADIENT,
+  N2_REQUIRE(io->objective == N2NMN_OBJ_CLONING || io->objective == N2NMN_OBJ_POLICY_GRADIENT ||
+                 io->objective == N2NMN_OBJ_POLICY_GRADIENT_SAMPLED,
              N2NMN_EINVAL, std::string(what) + ": unknown objective");
-  if (io->objective == N2NMN_OBJ_POLICY_GRADIENT) {
+  N2_REQUIRE(io->objective != N2NMN_OBJ_POLICY_GRADIENT_SAMPLED || c->d.variant == N2NMN_VARIANT_SHAPES,
+             N2NMN_EINVAL, std::string(what) + ": the sampled-layout objective belongs to the models_shapes variant");
+  if (io->objective != N2NMN_OBJ_CLONING) {
     N2_REQUIRE(io->expr_validity && io->baseline, N2NMN_EINVAL,
                std::string(what) + ": policy gradient needs expr_validity and baseline");
     N2_REQUIRE(io->baseline_decay >= 0.f && io->baseline_decay <= 1.f, N2NMN_EINVAL,
@@ -603,13 +608,15 @@ static int check_train_io(const n2nmn_ctx* c, const n2nmn_train_io* io, const n2
   return N2NMN_OK;
 }
 
-int n2nmn_train_forward(n2nmn_ctx* c, const n2nmn_train_io* io, n2nmn_program* p,
-                        n2nmn_stream stream) {
-  int rc = check_train_io(c, io, p, "train_forward");
-  if (rc != N2NMN_OK) return rc;
-  N2_REQUIRE(is_committed(c), N2NMN_ENOWEIGHT, "train_forward: weights not committed");
+// The front of a training forward: shapes_convnet (models_shapes, side stream), encoder and decoder with every
+// activation kept (c->rec).  uniforms == nullptr: teacher-forced on io->gt_layout, the hoisted conv_image GEMMs
+// of `p` beside the encoder.  Otherwise (n2nmn_train_sample) the decoder samples from `uniforms` under the
+// <eos> latch and leaves its tokens in tokens_out; p is not used.  Leaves c->rec set and the side stream
+// unjoined on success.
+static int train_front(n2nmn_ctx* c, const n2nmn_train_io* io, n2nmn_program* p, const float* uniforms,
+                       int32_t* tokens_out, float* scores, hipStream_t s) {
+  int rc = N2NMN_OK;
   TrainState* t = c->train;
-  hipStream_t s = S(stream);
   const n2nmn_dims& d = c->d;
   const int N = io->N, L = d.lstm_dim;
   const size_t nl = (size_t)N * L;
@@ -632,21 +639,22 @@ int n2nmn_train_forward(n2nmn_ctx* c, const n2nmn_train_io* io, n2nmn_program* p
   sio.input_seq = io->input_seq; sio.seq_length = io->seq_length; sio.T_enc = io->T_enc; sio.N = N;
   // policy gradient: the given tokens are the decoder's own samples -> automaton validity (mode 2)
   const bool rl = io->objective == N2NMN_OBJ_POLICY_GRADIENT;
-  sio.T_dec = io->T_dec; sio.use_gt_layout = rl ? 2 : 1; sio.gt_layout = io->gt_layout;
+  sio.T_dec = io->T_dec;
+  if (uniforms) { sio.sample_uniforms = uniforms; sio.predicted_tokens = tokens_out; }
+  else { sio.use_gt_layout = rl ? 2 : 1; sio.gt_layout = io->gt_layout; }
   t->last_N = N; t->last_T = io->T_enc; t->last_Td = io->T_dec;
+  t->sampled = false;
   const bool vqa = d.variant == N2NMN_VARIANT_VQA;
   const bool shapes = d.variant == N2NMN_VARIANT_SHAPES;
   if (shapes) {
     N2_REQUIRE(!(io->drop_qpn_h || io->drop_qpn_fc1), N2NMN_EINVAL,
                "train_forward: models_shapes has no question prior net");
-    N2_REQUIRE(!rl, N2NMN_EINVAL, "train_forward: models_shapes trains with ground-truth layouts only");
   } else {
     N2_REQUIRE(vqa || !(io->drop_enc0 || io->drop_dec0 || io->drop_qpn_h || io->drop_qpn_fc1),
                N2NMN_EINVAL, "train_forward: dropout belongs to the models_vqa variant");
   }
   sio.drop_enc0 = io->drop_enc0; sio.drop_dec0 = io->drop_dec0;
   c->rec = &t->rec;
-  float* scores = io->scores ? io->scores : t->scores;
   // models_shapes: the module network reads the features shapes_convnet computes from the images
   const float* feat = shapes ? t->cnn_feat : io->image_feat;
   if (shapes) {
@@ -677,11 +685,13 @@ int n2nmn_train_forward(n2nmn_ctx* c, const n2nmn_train_io* io, n2nmn_program* p
   }
   // the hoisted conv_image GEMMs of the module network need only the image features: they run on
   // the side stream beside the (strictly sequential) encoder
-  rc = run_program(c, p->prog, feat, c->word_vecs, N, scores, nullptr, nullptr, nullptr,
-                   0, 0, s, RP_PREP);
-  if (rc == N2NMN_OK)
-    rc = run_program(c, p->prog, feat, c->word_vecs, N, scores, nullptr, nullptr,
-                     nullptr, 0, 0, t->fork(s), RP_CONV);
+  if (p) {
+    rc = run_program(c, p->prog, feat, c->word_vecs, N, scores, nullptr, nullptr, nullptr,
+                     0, 0, s, RP_PREP);
+    if (rc == N2NMN_OK)
+      rc = run_program(c, p->prog, feat, c->word_vecs, N, scores, nullptr, nullptr,
+                       nullptr, 0, 0, t->fork(s), RP_CONV);
+  }
   if (rc == N2NMN_OK) rc = encoder_impl(c, &sio, s);
   if (rc == N2NMN_OK) {
     // the decoder starts from the encoder's final state (nmn3_netgen_att.py:177)
@@ -691,14 +701,68 @@ int n2nmn_train_forward(n2nmn_ctx* c, const n2nmn_train_io* io, n2nmn_program* p
     launch_unpack_h(c->fh1, t->rec.dh1s, N, L, d.N, s);
     rc = decoder_impl(c, &sio, s);
   }
-  if (rc == N2NMN_OK && shapes) {
+  if (rc == N2NMN_OK && shapes && !uniforms) {
     // the <eos> latch (models_shapes/nmn3_netgen_att.py:211-222): log_seq_prob and neg_entropy count the
-    // steps up to and including each row's first <eos> (the last layout token)
+    // steps up to and including each row's first <eos> (the last layout token).  (A sampling pass latches
+    // inside the decoder's token step: its plain sums are the latched ones.)
     ProfScope ps(c, F_BWD_MISC, 2.0 * io->T_dec * N, 12.0 * io->T_dec * N, s);
     launch_eos_latch(c->tprobs, c->ent_t, io->gt_layout, io->T_dec, N, d.num_vocab_nmn - 1, t->rec.lsp,
                      c->negent, s);
   }
-  t->join(s);
+  if (rc != N2NMN_OK) c->rec = nullptr;
+  return rc;
+}
+
+int n2nmn_train_sample(n2nmn_ctx* c, const n2nmn_train_io* io, const float* sample_uniforms,
+                       int32_t* tokens_out, n2nmn_stream stream) {
+  N2_REQUIRE(c && io && sample_uniforms && tokens_out, N2NMN_EINVAL, "train_sample: null argument");
+  N2_REQUIRE(c->train, N2NMN_EINVAL, "train_sample: call n2nmn_train_enable first");
+  N2_REQUIRE(c->d.variant == N2NMN_VARIANT_SHAPES, N2NMN_EINVAL,
+             "train_sample: the single-pass sampled step is built for the models_shapes variant");
+  N2_REQUIRE(io->input_seq && io->seq_length && io->image_feat, N2NMN_EINVAL,
+             "train_sample: null tensor in n2nmn_train_io");
+  N2_REQUIRE(io->N >= 1 && io->N <= c->d.N && io->T_enc >= 1 && io->T_enc <= c->d.T_encoder &&
+                 io->T_dec >= 1 && io->T_dec <= c->d.T_decoder,
+             N2NMN_ECAPACITY, "train_sample: N / T_enc / T_dec exceed the context capacity");
+  N2_REQUIRE(is_committed(c), N2NMN_ENOWEIGHT, "train_sample: weights not committed");
+  TrainState* t = c->train;
+  hipStream_t s = S(stream);
+  int rc = train_front(c, io, nullptr, sample_uniforms, tokens_out, nullptr, s);
+  c->rec = nullptr;
+  if (rc != N2NMN_OK) return rc;
+  t->join(s);                          // shapes_convnet (side stream): the features are final with the tokens
+  t->sampled = true;
+  return check_launch("train_sample");
+}
+
+int n2nmn_train_forward(n2nmn_ctx* c, const n2nmn_train_io* io, n2nmn_program* p,
+                        n2nmn_stream stream) {
+  int rc = check_train_io(c, io, p, "train_forward");
+  if (rc != N2NMN_OK) return rc;
+  N2_REQUIRE(is_committed(c), N2NMN_ENOWEIGHT, "train_forward: weights not committed");
+  TrainState* t = c->train;
+  hipStream_t s = S(stream);
+  const n2nmn_dims& d = c->d;
+  const int N = io->N;
+  const bool shapes = d.variant == N2NMN_VARIANT_SHAPES;
+  const bool rl = io->objective != N2NMN_OBJ_CLONING;
+  float* scores = io->scores ? io->scores : t->scores;
+  const float* feat = shapes ? t->cnn_feat : io->image_feat;
+  if (io->objective == N2NMN_OBJ_POLICY_GRADIENT_SAMPLED) {
+    // the sampling pass has run the convnet, the encoder and the decoder and kept their activations: what is
+    // left is the module network over the program assembled from its tokens
+    N2_REQUIRE(t->sampled && t->last_N == N && t->last_T == io->T_enc && t->last_Td == io->T_dec, N2NMN_EINVAL,
+               "train_forward: the sampled-layout objective follows n2nmn_train_sample of the same N / T_enc / T_dec");
+    N2_REQUIRE(t->pack_epoch == c->commit_epoch, N2NMN_EINVAL,
+               "train_forward: the weights changed since n2nmn_train_sample");
+    c->rec = &t->rec;
+    rc = run_program(c, p->prog, feat, c->word_vecs, N, scores, nullptr, nullptr, nullptr, 0, 0, s,
+                     RP_PREP | RP_CONV);
+  } else {
+    rc = train_front(c, io, p, nullptr, nullptr, scores, s);
+    if (rc != N2NMN_OK) return rc;
+    t->join(s);
+  }
   if (rc == N2NMN_OK)
     rc = run_program(c, p->prog, feat, c->word_vecs, N, scores, nullptr, nullptr, nullptr,
                      0, 0, s, RP_REST);
@@ -994,7 +1058,7 @@ int n2nmn_train_backward(n2nmn_ctx* c, const n2nmn_train_io* io, n2nmn_program* 
     a.v = mir(V_ATT_V); a.Wy = mir(V_TOK_W); a.T = T; a.N = N; a.L = L; a.V = V; a.Td = Td;
     a.inv_n = 1.0f / (float)N;
     if (shapes) { a.latch = 1; a.eos = V - 1; }
-    if (io->objective == N2NMN_OBJ_POLICY_GRADIENT) {
+    if (io->objective != N2NMN_OBJ_CLONING) {
       a.coef = t->rl_coef; a.valid_bits = t->rec.valid_bits;
       a.ent_coef = io->lambda_entropy / (float)N;
     }
@@ -1161,7 +1225,7 @@ int n2nmn_train_backward(n2nmn_ctx* c, const n2nmn_train_io* io, n2nmn_program* 
                        t->segs_dev, t->nsegs_early, 1.0f, io->weight_decay, io->losses + 2, s);
   }
   launch_loss_total(io->losses, io->weight_decay,
-                    io->objective == N2NMN_OBJ_POLICY_GRADIENT ? io->lambda_entropy : 0.f, s);
+                    io->objective != N2NMN_OBJ_CLONING ? io->lambda_entropy : 0.f, s);
   return check_launch("train_backward(1)");
 }
 
@@ -1270,6 +1334,7 @@ int64_t n2nmn_train_debug_tensor(n2nmn_ctx* c, const char* name, float* out, int
   else if (k == "d_dec_out") { src = t->dout; n = Td * N * L; }
   else if (k == "d_state") { src = t->dH0; n = 4 * (int64_t)d.N * L; }
   else if (k == "token_scores") { src = t->rec.tscores; n = Td * N * d.num_vocab_nmn; }
+  else if (k == "log_seq_prob") { src = t->rec.lsp; n = N; }
   else if (k == "d_image_feat" && t->cnn_dfeat_img) { src = t->cnn_dfeat_img; n = N * d.H * d.W * d.D; }
   else {
     set_last_error("train_debug_tensor: unknown tensor '" + k + "'");

@@ -118,6 +118,8 @@ struct TrainRec {
   // dropout on the output of LSTM layer 0 (models_vqa training): what the forward keeps is the
   // dropped h0 the layer above consumed (operand of the W1 gradient)
   float *eh0d = nullptr, *dh0d = nullptr;                   // [T][N][L], [Td][N][L] row-major
+  // models_shapes, sampled decoding: [N] "<eos> seen" flags of DecStepArgs::eos_seen (nullptr: no latch)
+  int32_t *eos_seen = nullptr;
 };
 struct TrainState;
 }  // namespace n2nmn

@@ -219,6 +219,11 @@ struct DecStepArgs {
   const int32_t* live_perm;
   const int32_t* live_n;
   int eos_token;
+  // <eos> latch of models_shapes on CHOSEN tokens (nmn3_netgen_att.py:210-226; sequential decoding): [N] flags,
+  // zero at the start of the pass, set once a row has chosen latch_eos.  A flagged row emits latch_eos with
+  // probability 1 and entropy 0 and feeds the <eos> embedding as next_idx.  nullptr: no latch
+  int32_t* eos_seen;
+  int latch_eos;
 };
 // can launch_dec_attn serve this launch with dec_attn_question_kernel (the kernel that honours dec_len)?
 bool dec_question_supported(const DecStepArgs& a, int nsteps);

@@ -523,9 +523,15 @@ __device__ __forceinline__ void dec_token_tail(const DecStepArgs& a, int n, int 
   float p = (on && valid) ? ex / den : 0.f;
   const float psum = wave_sum(p);
   p = p / psum;
-  const float tp = __shfl(p, tok, 64);
+  float tp = __shfl(p, tok, 64);
   float ent = on ? p * logf(fmaxf(1e-5f, p + (valid ? 0.f : 1.f))) : 0.f;
   ent = wave_sum(ent);
+  if (a.eos_seen) {                        // models_shapes: <eos> latch on the chosen tokens   (:210-226)
+    // (row n belongs to this workgroup alone, and the launches of a pass follow each other in stream order)
+    const bool seen = a.eos_seen[n] != 0;
+    if (!seen && tok == a.latch_eos && lane == 0) a.eos_seen[n] = 1;
+    if (seen) { tok = a.latch_eos; tp = 1.0f; ent = 0.f; }
+  }
   if (lane == 0) {
     a.tokens[tn] = tok;
     a.tprobs[tn] = tp;

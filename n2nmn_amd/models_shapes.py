@@ -28,17 +28,29 @@ Training (exp_shapes/train_shapes_gt_layout.py:143-163) is `ShapesTrainer`: an e
 N2NMN_VARIANT_SHAPES (include/n2nmn.h), whose training step runs shapes_convnet forward and backward, the <eos>
 latch of the teacher-forced loss and layer-0 LSTM dropout on the GPU.  A trained model is evaluated through
 this face: NMN3ModelAtt.load_weights(trainer.get_weights()).
+
+Training from scratch (exp_shapes/train_shapes_scratch.py:204-232) is `ShapesTrainer.step_rl`: the layouts are
+sampled inside the training forward, once (n2nmn_train_sample: convnet, encoder, decoder in sampling mode with the
+activations kept and the <eos> latch in the decoder's token step -- token <eos>, probability 1, entropy 0, <eos>
+embedding fed on, behind a row's first <eos>), fetched and assembled on the host, and the step continues with the
+module network and the policy-gradient loss (objective N2NMN_OBJ_POLICY_GRADIENT_SAMPLED).  Most sampled layouts
+do not assemble early in training; a batch with no valid layout has an empty program, zero scores and, for the
+modules and the convnet, the weight-decay gradient alone.  `forward_backward(..., objective=1)` is the two-pass
+form on tokens of the caller's choosing.
 """
 from __future__ import annotations
 
+import ctypes as C
+
 import numpy as np
 
+from . import _lib
 from .engine import Engine, _torch
 from .nmn3_assembler import Assembler as _Assembler
 from .nmn3_model import Compiler
 from .runtime import Fetch, Phase1Inputs, register_model, resolve, to_numpy
 from .spec import Dims, variable_shapes
-from .train import Trainer
+from .train import DROPOUT_FIELDS, Trainer
 
 SHAPES_MODULE_NAMES = ('_Find', '_Transform', '_And', '_Answer', '<eos>')   # exp_shapes/data/vocabulary_layout.txt
 # module -> C-ABI operator; _Answer = fc([min, mean, max]) is ExistModule's arithmetic (nmn3_modules.py:122-144)
@@ -249,7 +261,11 @@ class ShapesTrainer(Trainer):
     input_seq_batch [T, N], seq_length_batch [N], answer_label_batch [N].  dropout: None = multipliers drawn
     from the trainer's dropout_stream (seed) for the switched-on sites; False = no dropout for this step; or a
     dict {'enc0': [T, N, lstm_dim], 'dec0': [T_dec, N, lstm_dim]} of {0, 1} keep masks.  gradients() /
-    get_weights() / load_weights() use the reference's models_shapes names."""
+    get_weights() / load_weights() use the reference's models_shapes names.
+
+    step_rl(batch, sample_uniforms, ...): one iteration of exp_shapes/train_shapes_scratch.py (policy gradient on
+    sampled layouts; self.rl holds the driver's invalid_expr_loss 3, lambda_entropy 0.5, baseline_decay 0.99, and
+    the baseline starts at 3)."""
 
     def __init__(self, engine: Engine, weight_decay: float = 5e-4, lr: float = 1e-3,
                  max_grad_l2_norm: float = 10.0, encoder_dropout: bool = True, decoder_dropout: bool = True,
@@ -262,17 +278,51 @@ class ShapesTrainer(Trainer):
         self.dropout_stream.keep_prob = float(keep_prob)
         self.dropout_stream.seed = int(seed)
         self.ref_layout = {reference_name(k): v for k, v in self.layout.items()}
+        # exp_shapes/train_shapes_scratch.py:39-43,144: the baseline starts at invalid_expr_loss
+        self.rl = dict(invalid_expr_loss=3.0, lambda_entropy=0.5, baseline_decay=0.99)
+        self.set_baseline(self.rl['invalid_expr_loss'])
+        self._tokens = None              # [T_dec, N] tokens of the last sampling pass (device)
 
     def _io(self, batch, *args):
         return super()._io(dict(batch, image_feat_batch=batch['image_batch']), *args)
 
-    def forward_backward(self, batch, gt_layout, reduce: bool = True, objective: int = 0, dropout=None) -> float:
-        if objective != 0:
-            raise NotImplementedError('models_shapes trains with ground-truth layouts (behavioural cloning) here')
-        return super().forward_backward(batch, gt_layout, reduce=reduce, dropout=dropout)
-
-    def step_rl(self, *a, **k):
-        raise NotImplementedError('the policy-gradient objective of models_shapes is not part of this trainer')
+    def step_rl(self, batch, sample_uniforms, lr=None, update: bool = True, dropout=None):
+        """One iteration of exp_shapes/train_shapes_scratch.py:204-232.  n2nmn_train_sample runs shapes_convnet,
+        the encoder and the decoder once, sampling a layout per question (sample_uniforms [T_dec, N] in [0, 1)
+        replace tf.multinomial's generator) under this step's dropout multipliers and the <eos> latch, with the
+        activations kept; the tokens are fetched and assembled on the host (the reference's partial_run does the
+        same); the module network, the policy-gradient loss, both backward phases and Adam follow.  lr=None: the
+        trainer's own rate (the driver has no fine-tuning rate); update=False: losses and gradients only.
+        Returns (losses, tokens, expr_validity)."""
+        torch = _torch()
+        e = self.engine
+        seq = e._dev(batch['input_seq_batch'], torch.int32)
+        lens = e._dev(batch['seq_length_batch'], torch.int32)
+        img = e._dev(batch['image_batch'], torch.float32)
+        T, N = seq.shape
+        Td = self.ref_dims.T_decoder
+        uni = e._dev(sample_uniforms, torch.float32)
+        if tuple(uni.shape) != (Td, N):
+            raise ValueError('sample_uniforms: shape %s, expected %s' % (tuple(uni.shape), (Td, N)))
+        mult = self.multipliers(T, N, Td, dropout)
+        if self._tokens is None or tuple(self._tokens.shape) != (Td, N):
+            self._tokens = torch.empty((Td, N), dtype=torch.int32, device=e.device)
+        io = _lib.TrainIO()
+        io.input_seq = seq.data_ptr(); io.seq_length = lens.data_ptr(); io.image_feat = img.data_ptr()
+        io.T_enc = T; io.N = N; io.T_dec = Td
+        for key, m in mult.items():
+            setattr(io, DROPOUT_FIELDS[key], m.data_ptr())
+        _lib.check(self._lib.n2nmn_train_sample(self._ctx, C.byref(io), uni.data_ptr(), self._tokens.data_ptr(),
+                                                e.stream()))
+        tokens = self._tokens.cpu().numpy()
+        batch = dict(batch, input_seq_batch=seq, seq_length_batch=lens, image_batch=img)
+        scale = self._forward_backward(batch, tokens, True, 2, mult=mult, gt_dev=self._tokens)
+        if update:
+            saved = self.hyper['lr']
+            self.hyper['lr'] = saved if lr is None else float(lr)
+            self.apply(scale)
+            self.hyper['lr'] = saved
+        return self.losses, tokens, self.last_validity.copy()
 
     # -- reference names ---------------------------------------------------------------------------------
     def gradients(self):

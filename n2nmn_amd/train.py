@@ -260,7 +260,8 @@ class Trainer:
         mult = self.dropout_stream.multipliers(self.dropout_shapes(T, N, Td), dropout)
         return {k: self._pad_multiplier(k, m) for k, m in mult.items()}
 
-    def _io(self, batch, gt_layout, objective: int = 0, dropout=None, mult=None):
+    def _io(self, batch, gt_layout, objective: int = 0, dropout=None, mult=None, gt_dev=None):
+        """gt_dev: the device copy of gt_layout where one exists already (tokens sampled on the device)"""
         torch = _torch()
         e = self.engine
         d = e.dims
@@ -270,7 +271,8 @@ class Trainer:
         labels = e._dev(batch['answer_label_batch'], torch.int32)
         gt_host = np.ascontiguousarray(np.asarray(
             gt_layout.cpu().numpy() if hasattr(gt_layout, 'cpu') else gt_layout), np.int32)
-        gt = e.upload_i32(gt_host)       # pinned slot: no stream synchronisation per step
+        # pinned slot: no stream synchronisation per step
+        gt = e.upload_i32(gt_host) if gt_dev is None else gt_dev
         T, N = seq.shape
         Td = gt.shape[0]
         # teacher forcing: the layout is known before the forward, so the program is assembled
@@ -286,9 +288,9 @@ class Trainer:
         io.scores = self.scores.data_ptr(); io.losses = self.losses.data_ptr()
         io.grads = self.grads.data_ptr()
         val = None
-        if objective == 1:
+        if objective != 0:               # policy gradient (1; 2: on layouts sampled inside this step)
             val = e.upload_i32(np.asarray(validity, np.int32))
-            io.objective = 1
+            io.objective = objective
             io.expr_validity = val.data_ptr()
             io.invalid_expr_loss = self.rl['invalid_expr_loss']
             io.lambda_entropy = self.rl['lambda_entropy']
@@ -309,9 +311,9 @@ class Trainer:
         dropout: as for multipliers() (None: drawn, if the trainer has dropout sites)."""
         return self._forward_backward(batch, gt_layout, reduce, objective, dropout)
 
-    def _forward_backward(self, batch, gt_layout, reduce, objective, dropout=None, mult=None) -> float:
+    def _forward_backward(self, batch, gt_layout, reduce, objective, dropout=None, mult=None, gt_dev=None) -> float:
         """mult: ready multipliers (step_rl: the ones the layout was sampled under) instead of `dropout`"""
-        io, packed, _ = self._io(batch, gt_layout, objective, dropout, mult)
+        io, packed, _ = self._io(batch, gt_layout, objective, dropout, mult, gt_dev)
         s = self.engine.stream()
         _lib.check(self._lib.n2nmn_train_forward(self._ctx, C.byref(io), packed.handle, s))
         # the decoder's weight gradients and the finish of the late bucket stay on the library's side
