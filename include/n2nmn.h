@@ -239,6 +239,59 @@ int n2nmn_decoder_forward(n2nmn_ctx *ctx, const n2nmn_seq2seq_io *io, n2nmn_stre
 int n2nmn_seq2seq_forward(n2nmn_ctx *ctx, const n2nmn_seq2seq_io *io, n2nmn_stream stream);
 
 /* ------------------------------------------------------------------------------------------
+ * (2b) beam-search layout decoding (NEW relative to the reference, whose released code decodes greedily or by
+ *     sampling): keep the K most probable valid layout prefixes per question, return the most probable
+ *     complete layout.  Everything stays on the device; the outputs have the shapes and meaning of the greedy
+ *     call, so n2nmn_walk_layouts / n2nmn_execute_tokens follow directly.
+ *
+ *   Score of a prefix = sum over its steps of log(token_probs), token_probs as the decoder defines it (soft-max
+ *     over all tokens, masked by the automaton, renormalised: models_clevr/nmn3_netgen_att.py:245-256) -- a
+ *     finished beam's score is the log_seq_prob the decoder reports for those tokens.
+ *   Step 0: one live beam per question (encoder state, go_embedding, automaton state (0, 0, T_dec)); the other
+ *     K - 1 beams carry score -inf.
+ *   Step t: every beam runs the ordinary decoder step (both LSTM layers, attention over ITS QUESTION's encoder
+ *     rows, token logits).  Candidates are all (beam b, token s), b < K, s < num_vocab_nmn; the score of a
+ *     candidate is score[b] + log p_b(s) if s is valid in b's automaton state and score[b] is finite, else -inf.
+ *     TOTAL ORDER of candidates: score descending, then beam b ascending, then token s ascending (-inf
+ *     candidates included: they tie and are ordered by (b, s)).  The first K candidates become beams 0 .. K-1 of
+ *     step t + 1; each takes its parent's LSTM state (h, c of both layers), automaton state + P[s], next input
+ *     embedding_mat[s].  A beam with score -inf is dead: it keeps being carried (its tokens are whatever the
+ *     order gave it) and never wins against a finite candidate.
+ *   Finished beams: where the installed automaton allows nothing but <eos> behind <eos> and behind every answer
+ *     operator (n2nmn_automaton_forces_eos == 1: the CLEVR and VQA tables) they need no special case -- <eos> has
+ *     probability 1, the score stays.  All-valid tables (W = b = 0, every token valid in every state: the decoder
+ *     of models_shapes) and N2NMN_VARIANT_SHAPES get the <eos> latch of models_shapes/nmn3_netgen_att.py:210-226
+ *     per beam: behind its first <eos> (token num_vocab_nmn - 1) a beam's only candidate is <eos> with
+ *     probability 1 and entropy 0.  Tables with neither property: N2NMN_EINVAL.
+ *   After step T_dec - 1 the beams are in the total order; beam 0 is the result, read back through the parent
+ *     pointers.  predicted_tokens / token_probs / atts / word_vecs / neg_entropy / log_seq_prob are beam 0's.
+ *   Rows: decoder row = b * N + n (a beam is a block of N rows); the encoder tensors are NOT copied per beam.
+ *   Limits: 2 <= beam_size <= 16 and beam_size * N <= 1024 (N2NMN_EINVAL otherwise).  beam_size == 1 IS
+ *     n2nmn_seq2seq_forward / n2nmn_decoder_forward: the same launches, the same bits.
+ *   Not combined (N2NMN_EINVAL, never a fall-back): use_gt_layout, sample_uniforms, forced_tokens,
+ *     N2NMN_S2S_EOS_RETIRE, drop_enc0 / drop_dec0, token_scores, a training context while it records, and
+ *     N2NMN_MODE_THROUGHPUT_BF16X3 (the bf16 planes of the hidden states would have to move with every
+ *     per-step reorder).  num_vocab_nmn <= 16.
+ *   The first beam call of a context allocates its beam workspace (hipMalloc, sized for 16 beams, at most 1024
+ *   rows: that call may wait for the device and must not be made while `stream` is being captured into a graph;
+ *   later calls only launch); n2nmn_ctx_destroy frees it.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+  int32_t beam_size;               /* K                                                              */
+  int32_t reserved;
+  /* optional outputs (device, NULL = not wanted) */
+  int32_t *beam_tokens;            /* [K, T_dec, N] tokens of every beam in the final order          */
+  float *beam_scores;              /* [K, N] final scores (sum of log token_probs; -inf: dead beam)  */
+  int32_t *beam_parents;           /* [T_dec, K, N] beam of step t that beam k of step t + 1 extends */
+} n2nmn_beam_io;
+/* encoder + beam decoder in one call (io as for n2nmn_seq2seq_forward) */
+int n2nmn_seq2seq_beam(n2nmn_ctx *ctx, const n2nmn_seq2seq_io *io, const n2nmn_beam_io *beam,
+                       n2nmn_stream stream);
+/* beam decoder over the encoder results held in the context by the preceding encoder call */
+int n2nmn_decoder_beam(n2nmn_ctx *ctx, const n2nmn_seq2seq_io *io, const n2nmn_beam_io *beam,
+                       n2nmn_stream stream);
+
+/* ------------------------------------------------------------------------------------------
  * (3) host: RPN tokens -> packed program.   Replaces Assembler.assemble
  *     (models_clevr/nmn3_assembler.py:153-222) + td.Compiler.build_feed_dict / Loom's
  *     serialisation and per-depth batching (models_clevr/nmn3_model.py:55-159;

@@ -35,6 +35,12 @@ class Seq2SeqIO(C.Structure):
         ('seq_length_host', C.c_void_p), ('gt_length_host', C.c_void_p)]
 
 
+class BeamIO(C.Structure):
+    """n2nmn_beam_io (include/n2nmn.h section 2b)"""
+    _fields_ = [('beam_size', C.c_int32), ('reserved', C.c_int32),
+                ('beam_tokens', C.c_void_p), ('beam_scores', C.c_void_p), ('beam_parents', C.c_void_p)]
+
+
 class TrainIO(C.Structure):
     _fields_ = [
         ('input_seq', C.c_void_p), ('seq_length', C.c_void_p),
@@ -84,6 +90,8 @@ SYMBOLS = [
     ('n2nmn_encoder_forward', _I, [_P, C.POINTER(Seq2SeqIO), _P]),
     ('n2nmn_decoder_forward', _I, [_P, C.POINTER(Seq2SeqIO), _P]),
     ('n2nmn_seq2seq_forward', _I, [_P, C.POINTER(Seq2SeqIO), _P]),
+    ('n2nmn_seq2seq_beam', _I, [_P, C.POINTER(Seq2SeqIO), C.POINTER(BeamIO), _P]),
+    ('n2nmn_decoder_beam', _I, [_P, C.POINTER(Seq2SeqIO), C.POINTER(BeamIO), _P]),
     ('n2nmn_program_create', _I, [C.POINTER(_P)]),
     ('n2nmn_program_destroy', _I, [_P]),
     ('n2nmn_assemble', _I, [_P, _P, _I, _I, _P, _I, _P]),

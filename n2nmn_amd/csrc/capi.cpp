@@ -291,7 +291,8 @@ const char* kFamilyNames[F_COUNT] = {
   "lstm_bwd_step", "gemm_tn(weight grads)", "backward misc (modules/attention/gemm_nt)",
   "optimiser", "walk(layout walker)", "gemm_pkn(encoder_h_transform + q [+ conv_image when it rides in phase 1])",
   "walk_find(Find / Filter epilogues over the conv_image maps)", "walk_tmap(text maps from the attention tables)",
-  "sched(layout assembler + level scheduler on the device)"};
+  "sched(layout assembler + level scheduler on the device)",
+  "beam(select + state gather per step, backtrack)"};
 
 
 hipStream_t S(n2nmn_stream s) { return reinterpret_cast<hipStream_t>(s); }
@@ -986,6 +987,246 @@ int decoder_impl(n2nmn_ctx* c, const n2nmn_seq2seq_io* io, hipStream_t s, const 
   return check_launch("decoder_forward");
 }
 
+// ---- beam-search decoding (include/n2nmn.h section 2b) -----------------------------------------------------
+static size_t carve_beam(const n2nmn_dims& d, int R, char* base, BeamWS& w) {
+  Carver cv(base);
+  const size_t L = d.lstm_dim, Td = d.T_decoder, T = d.T_encoder;
+  for (int i = 0; i < 2; ++i) {
+    w.h0[i] = cv.take<float>(L * R); w.h1[i] = cv.take<float>(L * R);
+    w.c0[i] = cv.take<float>(L * R); w.c1[i] = cv.take<float>(L * R);
+    w.score[i] = cv.take<float>(R);
+    w.state[i] = cv.take<int32_t>((size_t)R * 3); w.seen[i] = cv.take<int32_t>(R);
+  }
+  w.q = cv.take<float>(L * R); w.h1_rm = cv.take<float>(L * R);
+  w.atts = cv.take<float>(Td * T * R);
+  w.p = cv.take<float>((size_t)R * BEAM_MAX_V); w.ent = cv.take<float>(R);
+  w.tprob = cv.take<float>(Td * R); w.ent_all = cv.take<float>(Td * R);
+  w.valid = cv.take<int32_t>(R); w.next_idx = cv.take<int32_t>(R); w.src_row = cv.take<int32_t>(R);
+  w.parent = cv.take<int32_t>(Td * R); w.token = cv.take<int32_t>(Td * R);
+  return align_up(cv.off, 256);
+}
+
+static int beam_workspace(n2nmn_ctx* c, hipStream_t s) {
+  if (c->beam.base) return N2NMN_OK;
+  const int R = round_up(std::min(BEAM_MAX_K * c->d.N, 1024), 64);
+  BeamWS w{};
+  const size_t bytes = carve_beam(c->d, R, nullptr, w);
+  int dev = 0;
+  N2_HIP(hipGetDevice(&dev));
+  if (dev != c->device) N2_HIP(hipSetDevice(c->device));
+  char* base = nullptr;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), bytes);
+  // (row tiles past K N read finite numbers; cleared on the caller's stream, in front of the launches that read)
+  if (e == hipSuccess) e = hipMemsetAsync(base, 0, bytes, s);
+  if (dev != c->device) (void)hipSetDevice(dev);
+  if (e != hipSuccess) {
+    if (base) (void)hipFree(base);
+    set_last_error(std::string("seq2seq_beam: workspace: ") + hipGetErrorString(e));
+    return N2NMN_EHIP;
+  }
+  carve_beam(c->d, R, base, w);
+  w.base = base; w.R = R;
+  c->beam = w;
+  return N2NMN_OK;
+}
+
+// the <eos> latch of models_shapes/nmn3_netgen_att.py:210-226 per beam: the SHAPES variant, and any context whose
+// installed tables make every token valid in every state (W = b = 0: the decoder of models_shapes on a CLEVR-variant
+// context, as its inference face builds it)
+static bool beam_latch(const n2nmn_ctx* c) {
+  const n2nmn_ctx* r = root(c);
+  auto zero = [](const std::vector<int32_t>& v) { return std::all_of(v.begin(), v.end(), [](int32_t x) { return x == 0; }); };
+  return c->d.variant == N2NMN_VARIANT_SHAPES || (r->have_tables && zero(r->W_host) && zero(r->b_host));
+}
+
+// everything that can be refused before a launch (the encoder half of n2nmn_seq2seq_beam runs behind it)
+static int beam_check(const n2nmn_ctx* c, const n2nmn_seq2seq_io* io, const n2nmn_beam_io* bio) {
+  const n2nmn_dims& d = c->d;
+  N2_REQUIRE(is_committed(c), N2NMN_ENOWEIGHT, "seq2seq_beam: weights not committed");
+  N2_REQUIRE(has_tables(c), N2NMN_ENOWEIGHT, "seq2seq_beam: validity tables (assembler P/W/b) not set");
+  N2_REQUIRE(io && bio, N2NMN_EINVAL, "seq2seq_beam: null io");
+  const int K = bio->beam_size;
+  N2_REQUIRE(K >= 2 && K <= BEAM_MAX_K, N2NMN_EINVAL,
+             "seq2seq_beam: beam_size must be 2 .. 16 (beam_size 1 is n2nmn_seq2seq_forward)");
+  N2_REQUIRE(io->N >= 1 && (long)K * io->N <= 1024, N2NMN_EINVAL,
+             "seq2seq_beam: beam_size * N exceeds 1024 decoder rows");
+  N2_REQUIRE(io->N <= d.N, N2NMN_ECAPACITY, "seq2seq_beam: N exceeds the context capacity");
+  N2_REQUIRE(io->T_dec >= 1 && io->T_dec <= d.T_decoder && io->T_dec <= 64, N2NMN_ECAPACITY,
+             "seq2seq_beam: T_dec too large");
+  N2_REQUIRE(d.num_vocab_nmn <= BEAM_MAX_V, N2NMN_EINVAL, "seq2seq_beam: num_vocab_nmn > 16");
+  N2_REQUIRE(!io->use_gt_layout && !io->gt_layout, N2NMN_EINVAL,
+             "seq2seq_beam: not combined with use_gt_layout (teacher forcing has no search)");
+  N2_REQUIRE(!io->sample_uniforms, N2NMN_EINVAL, "seq2seq_beam: not combined with sample_uniforms");
+  N2_REQUIRE(!io->forced_tokens, N2NMN_EINVAL, "seq2seq_beam: not combined with forced_tokens");
+  N2_REQUIRE(!(io->flags & N2NMN_S2S_EOS_RETIRE), N2NMN_EINVAL,
+             "seq2seq_beam: not combined with N2NMN_S2S_EOS_RETIRE");
+  N2_REQUIRE(!io->drop_enc0 && !io->drop_dec0, N2NMN_EINVAL, "seq2seq_beam: not combined with dropout multipliers");
+  N2_REQUIRE(!io->token_scores, N2NMN_EINVAL, "seq2seq_beam: token_scores is not an output of the beam decoder");
+  N2_REQUIRE(!c->rec, N2NMN_EINVAL, "seq2seq_beam: not inside a training step");
+  N2_REQUIRE(c->mode != N2NMN_MODE_THROUGHPUT_BF16X3, N2NMN_EINVAL,
+             "seq2seq_beam: not combined with N2NMN_MODE_THROUGHPUT_BF16X3");
+  N2_REQUIRE(beam_latch(c) || root(c)->retire_ok, N2NMN_EINVAL,
+             "seq2seq_beam: the installed automaton does not force <eos> behind a finished layout "
+             "(n2nmn_automaton_forces_eos == 0) and is not the all-valid one that gets the <eos> latch");
+  return N2NMN_OK;
+}
+
+static int beam_impl(n2nmn_ctx* c, const n2nmn_seq2seq_io* io, const n2nmn_beam_io* bio, hipStream_t s,
+                     const GemmArgs* pre, int npre) {
+  const n2nmn_dims& d = c->d;
+  int rc = beam_check(c, io, bio);
+  if (rc != N2NMN_OK) return rc;
+  train_infer_wait(root(c), s);
+  N2_REQUIRE(c->enc_T > 0 && io->N == c->enc_N && io->T_enc == c->enc_T, N2NMN_EINVAL,
+             "seq2seq_beam: no matching encoder results in the context");
+  N2_REQUIRE(!c->eht_partial || c->vars[V_EHT_B].mirror, N2NMN_EINVAL,
+             "seq2seq_beam: partial encoder_h_transform without the bias substitution");
+  rc = beam_workspace(c, s);
+  if (rc != N2NMN_OK) return rc;
+  BeamWS& w = c->beam;
+  const int T = c->enc_T, N = c->enc_N, L = d.lstm_dim, Td = io->T_dec, V = d.num_vocab_nmn;
+  const int K = bio->beam_size, rows = K * N, R = w.R;
+  N2_REQUIRE(rows <= R, N2NMN_ECAPACITY, "seq2seq_beam: beam_size * N exceeds the beam workspace");
+  const bool latch = beam_latch(c);
+  int32_t* tokens = io->predicted_tokens ? io->predicted_tokens : c->tokens;
+  float* tprobs = io->token_probs ? io->token_probs : c->tprobs;
+  float* negent = io->neg_entropy ? io->neg_entropy : c->negent;
+  float* atts = io->atts ? io->atts : c->atts;
+  float* wv = io->word_vecs ? io->word_vecs : c->word_vecs;
+  // what is due before the attention / the layout walk: encoder_h_transform, FindModule's conv_image
+  GemmArgs cv[2];
+  if (io->image_feat) conv_image_problems(c, io->image_feat, N, nullptr, Td, cv);
+  if (npre > 0 || io->image_feat) {
+    GemmArgs list[4];
+    int nl = 0;
+    double fl = 0, by = 0;
+    for (int i = 0; i < npre && nl < 3; ++i) {
+      list[nl++] = pre[i];
+      const double prow = pre[i].m_dev && c->eht_listed_rows >= 0 ? (double)c->eht_listed_rows : pre[i].M;
+      fl += 2.0 * prow * pre[i].K * pre[i].N;
+      by += 4.0 * (prow * (pre[i].K + pre[i].N) + (double)pre[i].K * pre[i].N);
+    }
+    if (io->image_feat) {
+      list[nl++] = cv[0];
+      fl += 2.0 * cv[0].M * cv[0].K * cv[0].N;
+      by += 4.0 * ((double)cv[0].M * (cv[0].K + c->Mp) + (double)cv[0].K * cv[0].N);
+    }
+    ProfScope ps(c, nl > 1 ? F_GEMM_MULTI : (io->image_feat ? F_CONV_IMAGE : F_GEMM_EHT), fl, by, s);
+    launch_gemm_pkn(list, nl, s);
+  }
+  c->dec_retired = false;
+  // every beam starts from its question's encoder state (row b N + n <- row n); scores 0, -inf, ...
+  {
+    const float* src[4] = {c->fh0, c->fc0, c->fh1, c->fc1};
+    float* dst[4] = {w.h0[0], w.c0[0], w.h1[0], w.c1[0]};
+    launch_beam_gather(src, dst, nullptr, N, rows, L, d.N, R, s);
+    launch_beam_init(w.score[0], w.state[0], w.seen[0], K, N, Td, s);
+  }
+  DecStepArgs a{};
+  a.eht = c->eht; a.eout = c->enc_out; a.seq_len = c->enc_len; a.v = c->vars[V_ATT_V].mirror;
+  a.eht_bias = c->vars[V_EHT_B].mirror;
+  a.Wy = c->vars[V_TOK_W].mirror; a.by = c->vars[V_TOK_B].mirror; a.P = c->P; a.Wv = c->Wv; a.bv = c->bv;
+  a.T = T; a.N = rows; a.L = L; a.V = V; a.Td = Td;
+  a.beam_Nq = N; a.beam_p = w.p; a.beam_valid = w.valid; a.latch_eos = V - 1;
+  a.q = w.q; a.out = w.h1_rm; a.ent_t = w.ent;
+  a.tokens = w.token; a.tprobs = w.tprob; a.next_idx = w.next_idx;     // (not written: the step chooses nothing)
+  const double fl0 = 2.0 * rows * L * 4 * L, fl1 = 2.0 * rows * 2 * L * 4 * L;
+  const double att_fl = (double)rows * (4.0 * T * L + 2.0 * 2 * L * V);
+  const double att_by = 4.0 * rows * (2.0 * T * L + 2.0 * L + T + V) + 4.0 * 2 * L * V;
+  auto packed = [&](LstmJob& j) { j.a_rs = 4; j.a_ks = 4 * R; j.hp_R = R; };
+  int hr0 = 0, hr1 = 0, ci0 = 0, ci1 = 0, si = 0;     // buffers holding the current h / c / (score, state, flags)
+  for (int t = 0; t < Td; ++t) {
+    LstmJob j0{};
+    j0.active = 1;
+    packed(j0);
+    j0.A0 = w.h0[hr0]; j0.K = L; j0.Wp = c->dec_W0h_t; j0.Wp64 = c->dec_W0h_64; j0.ntiles = L / 4;
+    j0.xtab = c->dec_xtab; j0.xidx = t == 0 ? nullptr : w.next_idx; j0.xidx_const = V;     // <go>
+    j0.c_in = w.c0[ci0]; j0.c_out = w.c0[ci0];
+    j0.h_old = j0.A0; j0.h_new = w.h0[hr0 ^ 1];
+    {
+      ProfScope ps(c, F_LSTM_DEC0, fl0, 4.0 * ((double)L * 4 * L + 3.0 * rows * L), s);
+      launch_lstm_step(&j0, 1, rows, L, 32, s, lstm_wide(c));
+    }
+    LstmJob j1{};
+    j1.active = 1;
+    packed(j1);
+    j1.out_seq = w.h1_rm;                 // row-major copy of the top-layer h for the attention
+    j1.A0 = w.h0[hr0 ^ 1]; j1.A1 = w.h1[hr1]; j1.K = 2 * L;
+    j1.Wp = c->dec_W1_t; j1.Wp64 = c->dec_W1_64; j1.ntiles = L / 4; j1.bias = c->dec_b1_t;
+    j1.c_in = w.c1[ci1]; j1.c_out = w.c1[ci1];
+    j1.h_old = j1.A1; j1.h_new = w.h1[hr1 ^ 1];
+    {
+      ProfScope ps(c, F_LSTM_DEC1, fl1, 4.0 * (2.0 * L * 4 * L + 5.0 * rows * L), s);
+      launch_lstm_step(&j1, 1, rows, L, 32, s, lstm_wide(c));
+    }
+    LstmJob jq{};                         // q = out . W_a + b_a            (nmn3_netgen_att.py:185)
+    packed(jq);
+    jq.hp_R = 0;
+    jq.active = 1; jq.mode = 1; jq.A0 = w.h1[hr1 ^ 1]; jq.K = L; jq.Wp = c->att_W_t;
+    jq.ntiles = L / 16; jq.bias = c->vars[V_ATT_B].mirror; jq.ldo = L; jq.h_new = w.q;
+    {
+      ProfScope ps(c, F_LINEAR_Q, 2.0 * rows * L * L, 4.0 * ((double)L * L + 2.0 * rows * L), s);
+      launch_lstm_step(&jq, 1, rows, L, 32, s);
+    }
+    a.state = w.state[si];
+    a.atts = w.atts + (size_t)t * T * rows;
+    a.beam_seen = latch ? w.seen[si] : nullptr;
+    {
+      ProfScope ps(c, F_DEC_STEP, att_fl, att_by, s);
+      launch_dec_attn(a, 1, s);
+    }
+    BeamSelectArgs b{};
+    b.p = w.p; b.valid = w.valid; b.ent = w.ent; b.score_in = w.score[si]; b.state_in = w.state[si];
+    b.seen_in = latch ? w.seen[si] : nullptr; b.P = c->P;
+    b.score_out = w.score[si ^ 1]; b.state_out = w.state[si ^ 1]; b.seen_out = w.seen[si ^ 1];
+    b.parent = w.parent + (size_t)t * rows; b.token = w.token + (size_t)t * rows;
+    b.tprob = w.tprob + (size_t)t * rows; b.ent_out = w.ent_all + (size_t)t * rows;
+    b.next_idx = w.next_idx; b.src_row = w.src_row;
+    b.K = K; b.N = N; b.V = V; b.eos = latch ? V - 1 : -1;
+    {
+      // (select + reorder of a step: the candidates in, 4 state arrays of K N rows read and written)
+      ProfScope ps(c, F_BEAM, 2.0 * rows * BEAM_MAX_V * K * BEAM_MAX_V,
+                   4.0 * rows * (BEAM_MAX_V + 16) + (t + 1 < Td ? 8.0 * 4 * rows * L : 0.0), s);
+      launch_beam_select(b, s);
+      si ^= 1;
+      if (t + 1 < Td) {
+        // parent -> child rows of h / c of both layers, into the alternate buffers
+        const float* src[4] = {w.h0[hr0 ^ 1], w.c0[ci0], w.h1[hr1 ^ 1], w.c1[ci1]};
+        float* dst[4] = {w.h0[hr0], w.c0[ci0 ^ 1], w.h1[hr1], w.c1[ci1 ^ 1]};
+        launch_beam_gather(src, dst, w.src_row, 0, rows, L, R, R, s);
+        ci0 ^= 1; ci1 ^= 1;               // (h: the gathered copy sits in the buffer the next step reads)
+      }
+    }
+  }
+  {
+    BeamBacktrackArgs bt{};
+    bt.parent = w.parent; bt.token = w.token; bt.tprob = w.tprob; bt.ent = w.ent_all; bt.atts_rows = w.atts;
+    bt.tokens = tokens; bt.tprobs = tprobs; bt.ent_t = c->ent_t; bt.atts = atts;
+    bt.beam_tokens = bio->beam_tokens; bt.K = K; bt.N = N; bt.T = T; bt.Td = Td;
+    ProfScope ps(c, F_BEAM, 0.0, 4.0 * Td * ((double)rows + 2.0 * T * N), s);
+    launch_beam_backtrack(bt, s);
+  }
+  if (bio->beam_scores)
+    N2_HIP(hipMemcpyAsync(bio->beam_scores, w.score[si], sizeof(float) * rows, hipMemcpyDeviceToDevice, s));
+  if (bio->beam_parents)
+    N2_HIP(hipMemcpyAsync(bio->beam_parents, w.parent, sizeof(int32_t) * (size_t)Td * rows,
+                          hipMemcpyDeviceToDevice, s));
+  if (io->image_feat) {              // FindSameProperty maps of the layouts the search chose
+    conv_image_problems(c, io->image_feat, N, root(c)->have_token_ops ? tokens : nullptr, Td, cv);
+    const double frac = root(c)->have_token_ops ? 0.1 : 1.0;
+    ProfScope ps(c, F_CONV_IMAGE, frac * 2.0 * cv[1].M * cv[1].K * cv[1].N,
+                 frac * 4.0 * cv[1].M * (cv[1].K + c->Mp), s);
+    launch_gemm_pkn(cv + 1, 1, s);
+  }
+  if (!(io->flags & N2NMN_S2S_NO_WORD_VECS)) {
+    const double E = d.embed_dim_txt;
+    ProfScope ps(c, F_WORD_VECS, 2.0 * Td * T * N * E, 4.0 * N * (T * E + Td * T + Td * E), s);
+    launch_word_vecs(atts, c->enc_seq, c->vars[V_ENC_EMB].mirror, Td, T, N, d.embed_dim_txt, wv,
+                     tprobs, c->ent_t, negent, io->log_seq_prob, s);
+  }
+  return check_launch("seq2seq_beam");
+}
+
 // scores += fc2(drop(relu(fc1(drop(h_concat)))))   (models_vqa/question_prior_net.py:10-28).
 // drop_h / drop_fc1: dropout multipliers (training) or nullptr.  What the backward pass needs stays
 // in the workspace: qpn_h (the dropped input) and qpn_hid (the dropped ReLU output).
@@ -1404,6 +1645,7 @@ int n2nmn_ctx_destroy(n2nmn_ctx* ctx) {
   if (!ctx) return N2NMN_OK;
   if (ctx->base && !ctx->parent) (void)hipFree(ctx->base);
   if (ctx->ws_base) (void)hipFree(ctx->ws_base);
+  if (ctx->beam.base) (void)hipFree(ctx->beam.base);
   for (int i = 0; i < n2nmn_ctx::kStage; ++i) {
     if (ctx->stage[i]) (void)hipHostFree(ctx->stage[i]);
     if (ctx->stage_ev[i]) (void)hipEventDestroy(ctx->stage_ev[i]);
@@ -1746,6 +1988,24 @@ int n2nmn_seq2seq_forward(n2nmn_ctx* ctx, const n2nmn_seq2seq_io* io, n2nmn_stre
   const int rc = encoder_impl(ctx, io, S(stream), defer ? &eht : nullptr);
   if (rc != N2NMN_OK) return rc;
   return decoder_impl(ctx, io, S(stream), defer ? &eht : nullptr, defer ? 1 : 0);
+}
+
+int n2nmn_decoder_beam(n2nmn_ctx* ctx, const n2nmn_seq2seq_io* io, const n2nmn_beam_io* beam,
+                       n2nmn_stream stream) {
+  N2_REQUIRE(ctx, N2NMN_EINVAL, "decoder_beam: null context");
+  return beam_impl(ctx, io, beam, S(stream), nullptr, 0);
+}
+
+int n2nmn_seq2seq_beam(n2nmn_ctx* ctx, const n2nmn_seq2seq_io* io, const n2nmn_beam_io* beam,
+                       n2nmn_stream stream) {
+  N2_REQUIRE(ctx, N2NMN_EINVAL, "seq2seq_beam: null context");
+  int rc = beam_check(ctx, io, beam);           // refuse before the encoder runs
+  if (rc != N2NMN_OK) return rc;
+  GemmArgs eht{};
+  const bool defer = !io->encoder_h_transformed;
+  rc = encoder_impl(ctx, io, S(stream), defer ? &eht : nullptr);
+  if (rc != N2NMN_OK) return rc;
+  return beam_impl(ctx, io, beam, S(stream), defer ? &eht : nullptr, defer ? 1 : 0);
 }
 
 int n2nmn_execute_program(n2nmn_ctx* ctx, n2nmn_program* p, const float* image_feat,

@@ -122,6 +122,23 @@ struct TrainRec {
   int32_t *eos_seen = nullptr;
 };
 struct TrainState;
+// Workspace of beam-search decoding (n2nmn_seq2seq_beam): allocated by the first beam call of a context, sized
+// for BEAM_MAX_K beams (R = min(16 * capacity N, 1024) rows, rounded up to 64), freed with the context.
+struct BeamWS {
+  char* base = nullptr;
+  int R = 0;                                   // rows of every buffer below (the k-interleaved states' R)
+  float *h0[2] = {nullptr, nullptr}, *h1[2] = {nullptr, nullptr};      // [L/4][R][4], ping-pong
+  float *c0[2] = {nullptr, nullptr}, *c1[2] = {nullptr, nullptr};
+  float *q = nullptr, *h1_rm = nullptr;        // [R][L] row-major
+  float *atts = nullptr;                       // [T_decoder][T_encoder][R] attention of every row at every step
+  float *p = nullptr, *ent = nullptr;          // [R][16], [R]
+  float *score[2] = {nullptr, nullptr};        // [K][N]
+  float *tprob = nullptr, *ent_all = nullptr;  // [T_decoder][R]
+  int32_t *state[2] = {nullptr, nullptr};      // [R][3]
+  int32_t *seen[2] = {nullptr, nullptr};       // [R]
+  int32_t *valid = nullptr, *next_idx = nullptr, *src_row = nullptr;   // [R]
+  int32_t *parent = nullptr, *token = nullptr; // [T_decoder][R]
+};
 }  // namespace n2nmn
 
 struct n2nmn_ctx {
@@ -227,6 +244,7 @@ struct n2nmn_ctx {
   long eht_listed_rows = -1;   // rows of that listed-row GEMM when the host knows the lengths (profile figures)
   int32_t *state = nullptr, *next_idx = nullptr, *tokens = nullptr;
   float *tprobs = nullptr, *negent = nullptr, *atts = nullptr, *word_vecs = nullptr;
+  BeamWS beam;                         // beam-search workspace (first n2nmn_seq2seq_beam call)
   int enc_T = 0, enc_N = 0;            // shape of the encoder results currently held
   const int32_t* enc_seq = nullptr;    // input_seq of the last encoder call (for word_vecs)
   const int32_t* enc_len = nullptr;
@@ -306,7 +324,7 @@ enum Family {
   F_LSTM_ENC = 0, F_LSTM_DEC0, F_LSTM_DEC1, F_LINEAR_Q, F_DEC_STEP, F_GEMM_EHT, F_WORD_VECS,
   F_TEXTMAP, F_CONV_IMAGE, F_ATT_OPS, F_POOL, F_HEADS,
   F_LSTM_BWD, F_GEMM_TN, F_BWD_MISC, F_OPTIMISER, F_WALK, F_GEMM_MULTI, F_WALK_FIND, F_WALK_TMAP,
-  F_SCHED, F_COUNT
+  F_SCHED, F_BEAM, F_COUNT
 };
 extern const char* kFamilyNames[F_COUNT];
 

@@ -224,7 +224,59 @@ struct DecStepArgs {
   // probability 1 and entropy 0 and feeds the <eos> embedding as next_idx.  nullptr: no latch
   int32_t* eos_seen;
   int latch_eos;
+  // beam search (one sequential step over K N decoder rows, beam-major: row = beam * beam_Nq + question;
+  // dec_attn_seq_kernel / dec_attn_kernel<1024>).  beam_Nq > 0: N counts DECODER rows (q, out, state, atts
+  // [T][N]), while eht / eout / seq_len are the encoder tensors of the beam_Nq questions -- a row reads those
+  // of question row % beam_Nq, no copy per beam.  The step then chooses no token: per row it writes the V
+  // masked-renormalised token probabilities (0 for invalid tokens; beam_p [N][16]), the validity bits
+  // (beam_valid [N]) and the entropy term (ent_t [N]); beam_select_kernel reads them.  beam_seen [N] (or
+  // nullptr): <eos> latch per row -- a flagged row reports <eos> with probability 1, entropy 0, nothing else valid.
+  int beam_Nq;
+  float* beam_p;
+  int32_t* beam_valid;
+  const int32_t* beam_seen;
 };
+// ---- beam search (kernels_beam.hip; semantics: include/n2nmn.h section 2b) ----
+constexpr int BEAM_MAX_K = 16;
+constexpr int BEAM_MAX_V = 16;         // == MAXV of the decoder step kernels
+// row r of the four k-interleaved state arrays dst_i [L/4][Rd][4] = row src_row[r] of src_i [L/4][Rs][4]
+// (src_row == nullptr: row r % mod -- every beam starts from its question's encoder state)
+void launch_beam_gather(const float* const src[4], float* const dst[4], const int32_t* src_row, int mod,
+                        int rows, int L, int Rs, int Rd, hipStream_t s);
+// score [K][N]: 0 for beam 0, -inf for the others; automaton state (0, 0, T_dec); <eos> flags 0
+void launch_beam_init(float* score, int32_t* state, int32_t* seen, int K, int N, int T_dec, hipStream_t s);
+struct BeamSelectArgs {
+  const float* p;            // [K N][16]  this step's token probabilities per row (DecStepArgs::beam_p)
+  const int32_t* valid;      // [K N]
+  const float* ent;          // [K N]
+  const float* score_in;     // [K][N]
+  const int32_t* state_in;   // [K N][3]
+  const int32_t* seen_in;    // [K N] or nullptr
+  const int32_t* P;          // [V][3]
+  float* score_out; int32_t* state_out; int32_t* seen_out;
+  int32_t* parent;           // [K][N] this step's slice of the parent pointers
+  int32_t* token;            // [K][N]
+  float* tprob;              // [K][N] probability of the chosen token
+  float* ent_out;            // [K][N] entropy term of the parent row
+  int32_t* next_idx;         // [K N] decoder x-table row of the next step (= token)
+  int32_t* src_row;          // [K N] parent ROW of every new row (launch_beam_gather)
+  int K, N, V, eos;
+};
+void launch_beam_select(const BeamSelectArgs& a, hipStream_t s);
+struct BeamBacktrackArgs {
+  const int32_t* parent;     // [Td][K][N]
+  const int32_t* token;      // [Td][K][N]
+  const float* tprob;        // [Td][K][N]
+  const float* ent;          // [Td][K][N]
+  const float* atts_rows;    // [Td][T][K N] attention of every row at every step
+  int32_t* tokens;           // [Td][N] best beam
+  float* tprobs;             // [Td][N]
+  float* ent_t;              // [Td][N]
+  float* atts;               // [Td][T][N]
+  int32_t* beam_tokens;      // [K][Td][N] or nullptr
+  int K, N, T, Td;
+};
+void launch_beam_backtrack(const BeamBacktrackArgs& a, hipStream_t s);
 // can launch_dec_attn serve this launch with dec_attn_question_kernel (the kernel that honours dec_len)?
 bool dec_question_supported(const DecStepArgs& a, int nsteps);
 bool dec_len_supported(const DecStepArgs& a, int nsteps);

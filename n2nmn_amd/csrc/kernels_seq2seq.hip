@@ -526,6 +526,15 @@ __device__ __forceinline__ void dec_token_tail(const DecStepArgs& a, int n, int 
   float tp = __shfl(p, tok, 64);
   float ent = on ? p * logf(fmaxf(1e-5f, p + (valid ? 0.f : 1.f))) : 0.f;
   ent = wave_sum(ent);
+  if (a.beam_p) {                          // beam search: the candidates of this row, no choice (beam_select_kernel)
+    unsigned long long vb = __ballot(on && valid);
+    if (a.beam_seen && a.beam_seen[n] != 0) {      // <eos> latch of this beam
+      p = lane == a.latch_eos ? 1.0f : 0.f; ent = 0.f; vb = 1ull << a.latch_eos;
+    }
+    if (lane < MAXV) a.beam_p[(size_t)n * MAXV + lane] = on ? p : 0.f;
+    if (lane == 0) { a.beam_valid[n] = (int32_t)vb; a.ent_t[tn] = ent; }
+    return;
+  }
   if (a.eos_seen) {                        // models_shapes: <eos> latch on the chosen tokens   (:210-226)
     // (row n belongs to this workgroup alone, and the launches of a pass follow each other in stream order)
     const bool seen = a.eos_seen[n] != 0;
@@ -561,7 +570,9 @@ __global__ __launch_bounds__(NT) void dec_attn_kernel(DecStepArgs a) {
   float* red = es + ((T + 3) & ~3);           // [NW][MAXV]
   const int n = blockIdx.x, ts = blockIdx.y;  // ts: step offset inside this launch
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int len = min(max(a.seq_len[n], 0), T);   // device-side lengths are not visible to the host checks
+  // beam search: row n of K N decoder rows reads the encoder tensors of question n % beam_Nq (EN questions)
+  const int EN = a.beam_Nq > 0 ? a.beam_Nq : N, en = a.beam_Nq > 0 ? n % a.beam_Nq : n;
+  const int len = min(max(a.seq_len[en], 0), T);   // device-side lengths are not visible to the host checks
   const size_t tn = (size_t)ts * N + n;
   const float* qrow = a.q + tn * L;
   const float* orow = a.out + tn * L;
@@ -591,7 +602,7 @@ __global__ __launch_bounds__(NT) void dec_attn_kernel(DecStepArgs a) {
         const int tau = w + NW * (j0 + u);
         s[u] = 0.f;
         if (tau < Tv) {
-          const float* er = (virt && tau == len) ? a.eht_bias : a.eht + ((size_t)tau * N + n) * L;
+          const float* er = (virt && tau == len) ? a.eht_bias : a.eht + ((size_t)tau * EN + en) * L;
 #pragma unroll
           for (int i = 0; i < MAXKI; ++i) {
             const int k = 4 * lane + 256 * i;
@@ -647,11 +658,11 @@ __global__ __launch_bounds__(NT) void dec_attn_kernel(DecStepArgs a) {
     for (int c = tid; c < ncol * nsplit; c += NT) {
       const int col = c % ncol, sp = c / ncol;
       float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-      const float* ob = a.eout + (size_t)n * L + 4 * col;
+      const float* ob = a.eout + (size_t)en * L + 4 * col;
 #pragma unroll 4
       for (int tau = sp; tau < len; tau += nsplit) {
         const float at = es[tau];
-        const float4 o4 = *reinterpret_cast<const float4*>(ob + (size_t)tau * N * L);
+        const float4 o4 = *reinterpret_cast<const float4*>(ob + (size_t)tau * EN * L);
         acc.x += at * o4.x; acc.y += at * o4.y; acc.z += at * o4.z; acc.w += at * o4.w;
       }
       *reinterpret_cast<float4*>(ctxp + (size_t)sp * L + 4 * col) = acc;
@@ -734,7 +745,9 @@ __global__ __launch_bounds__(1024, 2) void dec_attn_seq_kernel(DecStepArgs a) {
       return;
     }
   }
-  const int len = min(max(a.seq_len[n], 0), T);
+  // beam search: row n of K N decoder rows reads the encoder tensors of question n % beam_Nq (EN questions)
+  const int EN = a.beam_Nq > 0 ? a.beam_Nq : N, en = a.beam_Nq > 0 ? n % a.beam_Nq : n;
+  const int len = min(max(a.seq_len[en], 0), T);
   const size_t tn = n;                              // (one step per launch: step offset 0)
   const float* qrow = a.q + qr * L;
   const float* orow = a.out + tn * L;
@@ -747,9 +760,9 @@ __global__ __launch_bounds__(1024, 2) void dec_attn_seq_kernel(DecStepArgs a) {
     v4[i] = *reinterpret_cast<const float4*>(a.v + k);
     q4[i] = *reinterpret_cast<const float4*>(qrow + k);
   }
-  const size_t rstride = (size_t)N * L;
-  const float* eb = a.eht + (size_t)n * L + 4 * lane;
-  const float* ob = a.eout + (size_t)n * L + 4 * lane;
+  const size_t rstride = (size_t)EN * L;
+  const float* eb = a.eht + (size_t)en * L + 4 * lane;
+  const float* ob = a.eout + (size_t)en * L + 4 * lane;
   float4 e4[KI], o4[KI], acc[KI];
 #pragma unroll
   for (int i = 0; i < KI; ++i) acc[i] = make_float4(0.f, 0.f, 0.f, 0.f);

@@ -197,7 +197,7 @@ class Engine:
                 gt_layout=None, sample_uniforms=None, forced_tokens=None, debug: bool = False,
                 reuse_buffers: bool = True, phase: str = 'both', word_vecs: bool = True,
                 image_feat=None, dropout=None, out_tokens=None, seq_len_host=None,
-                eos_retire: bool = False, gt_len_host=None):
+                eos_retire: bool = False, gt_len_host=None, beam_size: int = 1, return_beams: bool = False):
         """Phase 1.  input_seq [T,N] int32, seq_len [N] int32 (device tensors or anything
         convertible).  Returns a dict of device tensors named like the reference attributes
         (models_clevr/nmn3_netgen_att.py:305-322).  With reuse_buffers the outputs are views of
@@ -212,7 +212,13 @@ class Engine:
         N2NMN_S2S_EOS_RETIRE -- rows leave the decoder at their layout's first <eos>; predicted_tokens are
         complete, atts / token_probs hold the live (row, step) pairs only (call again with phase='decoder'
         and eos_retire=False for every step).  gt_len_host: host int32 [N] layout lengths (tokens in front
-        of the first <eos>, `layout_lengths`), optional."""
+        of the first <eos>, `layout_lengths`), optional.
+        beam_size (default 1 = greedy, today's call): K >= 2 decodes by beam search of width K on the device
+        (n2nmn_seq2seq_beam, include/n2nmn.h section 2b); the returned tensors are the best beam's, with the
+        shapes and meaning of the greedy call.  return_beams adds 'beam_tokens' [K, T_dec, N], 'beam_scores'
+        [K, N] (sum of log token_probs, -inf for a dead beam) and 'beam_parents' [T_dec, K, N].  Combinations
+        the library does not decode (teacher forcing, sampling, forced tokens, eos_retire, dropout, debug
+        fetches, K > 16, K * N > 1024) raise ValueError with its message."""
         torch = _torch()
         d = self.dims
         seq = self._dev(input_seq, torch.int32)
@@ -282,9 +288,24 @@ class Engine:
             io.flags |= 1
             for k in ('word_vecs', 'neg_entropy', 'log_seq_prob'):
                 out.pop(k)
-        fn = {'both': self._lib.n2nmn_seq2seq_forward, 'encoder': self._lib.n2nmn_encoder_forward,
-              'decoder': self._lib.n2nmn_decoder_forward}[phase]
-        _lib.check(fn(self._ctx, C.byref(io), self.stream()))
+        if int(beam_size) != 1:
+            if phase == 'encoder':
+                raise ValueError('beam_size belongs to the decoder half')
+            K = int(beam_size)
+            bio = _lib.BeamIO()
+            bio.beam_size = K
+            if return_beams and 2 <= K <= 16:
+                out['beam_tokens'] = mk('btok', (K, Td, N), torch.int32)
+                out['beam_scores'] = mk('bsc', (K, N), torch.float32)
+                out['beam_parents'] = mk('bpar', (Td, K, N), torch.int32)
+                for k in ('beam_tokens', 'beam_scores', 'beam_parents'):
+                    setattr(bio, k, out[k].data_ptr())
+            fn = {'both': self._lib.n2nmn_seq2seq_beam, 'decoder': self._lib.n2nmn_decoder_beam}[phase]
+            _lib.check(fn(self._ctx, C.byref(io), C.byref(bio), self.stream()))
+        else:
+            fn = {'both': self._lib.n2nmn_seq2seq_forward, 'encoder': self._lib.n2nmn_encoder_forward,
+                  'decoder': self._lib.n2nmn_decoder_forward}[phase]
+            _lib.check(fn(self._ctx, C.byref(io), self.stream()))
         out['_keepalive'] = (seq, lens, gt, uni, forced, feat, drops)
         out['_input_seq'], out['_seq_length'] = seq, lens
         return out
@@ -549,7 +570,7 @@ class Engine:
 
     def forward(self, batch, T_dec: Optional[int] = None, use_gt_layout: bool = False,
                 gt_layout=None, sample_uniforms=None, host_assemble: bool = False,
-                fetch: bool = True, out=None, eos_retire: bool = False):
+                fetch: bool = True, out=None, eos_retire: bool = False, beam_size: int = 1):
         """The whole hot path of exp_clevr/eval_clevr.py:103-135 for one batch:
         phase 1 -> token fetch (the one host sync) -> C++ assemble/pack -> phase 2.
         Returns (scores device tensor, tokens numpy [T_dec,N], validity numpy [N]).
@@ -570,7 +591,10 @@ class Engine:
         runs a row only up to its layout's first <eos> (teacher-forced layouts: rows ranked by length up
         front; layouts the decoder chooses: rows leave the recurrence as they emit <eos>); scores / tokens / validity are bit-identical to
         the full decoder's (the fetches of exp_clevr/eval_clevr.py:103-135), the decoder's own outputs for
-        the steps behind it are computed on demand (`decoder_outputs`)."""
+        the steps behind it are computed on demand (`decoder_outputs`).
+
+        beam_size >= 2: the layout is the most probable one a beam search of that width finds (seq2seq's
+        beam_size); decode -> walk -> logits stays on the device."""
         if self.walk_supported() and not host_assemble:
             # device path: the walker decodes the layouts itself (no sync between the phases).  The
             # hoisted conv_image GEMMs ride in phase 1's own GEMM launch (with encoder_h_transform
@@ -605,7 +629,8 @@ class Engine:
                                image_feat=None if (self.overlap_conv or conv_late) else feat,
                                out_tokens=None if out is None else out[1],
                                seq_len_host=batch.get('seq_length_host'),
-                               eos_retire=retire, gt_len_host=glen)
+                               eos_retire=retire or (bool(eos_retire) and int(beam_size) != 1), gt_len_host=glen,
+                               beam_size=beam_size)
             # (device tensors of this call: the context keeps pointers to them until the next encoder call)
             self._last_s2s_args = (s2s['_input_seq'], s2s['_seq_length'], T_dec, use_gt_layout, gt_dev,
                                    sample_uniforms)
@@ -633,11 +658,11 @@ class Engine:
             tokens = np.ascontiguousarray(gt_layout, np.int32)
             packed, validity = self.assembler.assemble_packed(tokens)
             s2s = self.seq2seq(batch['input_seq_batch'], batch['seq_length_batch'], T_dec,
-                               True, self.upload_i32(tokens), sample_uniforms)
+                               True, self.upload_i32(tokens), sample_uniforms, beam_size=beam_size)
             scores = self.execute(packed, batch['image_feat_batch'], s2s['word_vecs'])
             return scores, tokens, validity
         s2s = self.seq2seq(batch['input_seq_batch'], batch['seq_length_batch'], T_dec,
-                           use_gt_layout, gt_layout, sample_uniforms)
+                           use_gt_layout, gt_layout, sample_uniforms, beam_size=beam_size)
         tokens = s2s['predicted_tokens'].cpu().numpy()
         packed, validity = self.assembler.assemble_packed(tokens)
         scores = self.execute(packed, batch['image_feat_batch'], s2s['word_vecs'])

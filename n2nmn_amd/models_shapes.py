@@ -76,7 +76,7 @@ class NMN3ModelAtt:
                  decoder_dropout, decoder_sampling, num_choices, use_gt_layout=None, gt_layout_batch=None,
                  scope='neural_module_network', reuse=None, engine: Engine = None, device: int = 0,
                  max_batch: int = 256, T_encoder: int = 15, map_dim: int = 500, feat_dim: int = 64,
-                 hidden_dim: int = 64, kernel_size: int = 3):
+                 hidden_dim: int = 64, kernel_size: int = 3, beam_size: int = 1):
         if encoder_dropout or decoder_dropout or decoder_sampling:
             raise NotImplementedError('the inference face takes no dropout / sampling (exp_shapes/eval_shapes.py:33-35)')
         names = list(SHAPES_MODULE_NAMES)
@@ -110,6 +110,7 @@ class NMN3ModelAtt:
         self.engine = engine
         self.EOS_idx = EOS_idx
         self.T_decoder = T_decoder
+        self.beam_size = int(beam_size)      # layouts by beam search of this width (the <eos> latch then runs per beam on the device)
         self.hidden_dim = hidden_dim
         self.image_batch = image_batch
         self.phase1_inputs = Phase1Inputs(text_seq_batch, seq_length_batch, use_gt_layout, gt_layout_batch)
@@ -165,7 +166,7 @@ class NMN3ModelAtt:
     def run_phase1(self, feeds=None):
         feeds = feeds or {}
         seq, lens, use_gt, gt = self.phase1_inputs.resolve(feeds)
-        out = dict(self.engine.seq2seq(seq, lens, self.T_decoder, use_gt, gt))
+        out = dict(self.engine.seq2seq(seq, lens, self.T_decoder, use_gt, gt, beam_size=self.beam_size))
         # the <eos> latch of models_shapes/nmn3_netgen_att.py:215-222: behind the first <eos> every token is <eos>
         tok = to_numpy(out['predicted_tokens']).copy()
         seen = np.cumsum(tok == self.EOS_idx, axis=0) > 0

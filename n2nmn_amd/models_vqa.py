@@ -59,7 +59,8 @@ class NMN3Model:
                  encoder_dropout, decoder_dropout, decoder_sampling, num_choices, use_qpn, qpn_dropout,
                  reduce_visfeat_dim=False, new_visfeat_dim=256, use_gt_layout=None, gt_layout_batch=None,
                  scope='neural_module_network', reuse=None, engine: VQAEngine = None, device: int = 0,
-                 max_batch: int = 64, T_encoder: int = 26, map_dim: int = 1024, qpn_hidden: int = 500):
+                 max_batch: int = 64, T_encoder: int = 26, map_dim: int = 1024, qpn_hidden: int = 500,
+                 beam_size: int = 1):
         if reduce_visfeat_dim:
             raise NotImplementedError('reduce_visfeat_dim=True (the extra 1x1 convolution of '
                                       'models_vqa/nmn3_model.py:27-34) is not part of the drop-in; '
@@ -71,6 +72,7 @@ class NMN3Model:
         self.dropout_seed = 0
         self._drop_gen = None
         self.sampling = SamplingUniforms(0)
+        self.beam_size = int(beam_size)      # eager (inference) fetches: layouts by beam search of this width
         self.dropout_masks = None            # tests: {'enc0','dec0','qpn_h','qpn_fc1'} keep masks for the NEXT handle
         self.last_masks = None
         if list(assembler.module_names) != list(VQA_MODULE_NAMES):
@@ -172,7 +174,7 @@ class NMN3Model:
     # -- eager execution ------------------------------------------------------------------------------
     def run_phase1(self, feeds=None):
         seq, lens, use_gt, gt = self.phase1_inputs.resolve(feeds or {})
-        return self.engine.seq2seq(seq, lens, self.T_decoder, use_gt, gt)
+        return self.engine.seq2seq(seq, lens, self.T_decoder, use_gt, gt, beam_size=self.beam_size)
 
     def run_phase2(self, packed, image_feat, word_vecs):
         """the packed program on image features WITHOUT the coordinate channels (the reference appends them

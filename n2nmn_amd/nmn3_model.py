@@ -14,6 +14,7 @@ second `partial_run` executes the packed program with the HIP module kernels.
 
 Extra keyword `engine=` (or `device=` / `max_batch=` / `T_encoder=` to build one) selects the GPU
 context that holds the weights; `model.load_weights(dict)` registers reference-named variables.
+`beam_size=` (default 1 = the reference's decoding) decodes the layout by beam search of that width.
 """
 from __future__ import annotations
 
@@ -46,7 +47,7 @@ class NMN3Model:
                  assembler, encoder_dropout, decoder_dropout, decoder_sampling, num_choices,
                  use_gt_layout=None, gt_layout_batch=None, scope='neural_module_network',
                  reuse=None, engine: Engine = None, device: int = 0, max_batch: int = 64,
-                 T_encoder: int = 45, map_dim: int = 250, kernel_size: int = 5):
+                 T_encoder: int = 45, map_dim: int = 250, kernel_size: int = 5, beam_size: int = 1):
         if engine is None:
             shp = getattr(image_feat_grid, 'shape', None)
             if shp is None or len(shp) != 4 or any(s is None for s in shp[1:]):
@@ -64,7 +65,8 @@ class NMN3Model:
         self.att_seq2seq = AttentionSeq2Seq(
             text_seq_batch, seq_length_batch, T_decoder, num_vocab_txt, embed_dim_txt,
             num_vocab_nmn, embed_dim_nmn, lstm_dim, num_layers, assembler, encoder_dropout,
-            decoder_dropout, decoder_sampling, use_gt_layout, gt_layout_batch, engine=engine)
+            decoder_dropout, decoder_sampling, use_gt_layout, gt_layout_batch, engine=engine,
+            beam_size=beam_size)
         self.phase1_inputs = self.att_seq2seq.phase1_inputs
         for name in PHASE1_OUTPUTS:
             setattr(self, name, Fetch(self, name, 1))

@@ -8,7 +8,8 @@
 Attributes `.predicted_tokens .token_probs .neg_entropy .atts .word_vecs` (:305-322) are fetch
 handles; `run(feeds)` executes phase 1 through the C-ABI (`n2nmn_seq2seq_forward`: 2-layer LSTM
 encoder, attentional LSTM decoder under the validity automaton, text-attention word vectors) and
-returns device tensors.  Inputs may be placeholders (bound by `feeds`) or tensors.
+returns device tensors.  Inputs may be placeholders (bound by `feeds`) or tensors.  Extra keyword
+`beam_size=` (default 1): decode the layout by beam search of that width (include/n2nmn.h section 2b).
 """
 from __future__ import annotations
 
@@ -25,7 +26,7 @@ class AttentionSeq2Seq:
                  num_vocab_nmn, embed_dim_nmn, lstm_dim, num_layers, assembler, encoder_dropout,
                  decoder_dropout, decoder_sampling, use_gt_layout=None, gt_layout_batch=None,
                  scope='encoder_decoder', reuse=None, engine: Engine = None, sample_seed: int = 0,
-                 dropout_seed: int = 0):
+                 dropout_seed: int = 0, beam_size: int = 1):
         if engine is None:
             raise ValueError('AttentionSeq2Seq needs engine=Engine(...)')
         d = engine.dims
@@ -60,6 +61,9 @@ class AttentionSeq2Seq:
         self.decoder_sampling = decoder_sampling
         self.phase1_inputs = Phase1Inputs(input_seq_batch, seq_length_batch, use_gt_layout, gt_layout_batch)
         self.sampling = SamplingUniforms(sample_seed)
+        # extra keyword behind the reference's arguments: layouts by beam search of this width on the device
+        # (Engine.seq2seq beam_size; 1 = the reference's greedy / sampled decoding)
+        self.beam_size = int(beam_size)
         for name in PHASE1_OUTPUTS:
             setattr(self, name, Fetch(self, name, 1))
 
@@ -73,7 +77,7 @@ class AttentionSeq2Seq:
         on = dict(enc0=self.encoder_dropout, dec0=self.decoder_dropout)
         mult = self.dropout_stream.multipliers({k: s for k, s in shapes.items() if on[k]}, self.dropout_masks)
         return self.engine.seq2seq(seq, lens, self.T_decoder, use_gt, gt, uni, forced_tokens, debug=debug,
-                                   dropout=(mult.get('enc0'), mult.get('dec0')))
+                                   dropout=(mult.get('enc0'), mult.get('dec0')), beam_size=self.beam_size)
 
     def _fetch(self, f, handle):
         from .runtime import to_numpy
