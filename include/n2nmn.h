@@ -615,6 +615,13 @@ int n2nmn_adam_step(n2nmn_ctx *ctx, const float *grads, float grad_scale, float 
                     n2nmn_stream stream);
 /* zero the Adam moments (a fresh tf.train.AdamOptimizer) */
 int n2nmn_train_reset_optimizer(n2nmn_ctx *ctx, n2nmn_stream stream);
+/* Adam's moments in the flat layout of the gradient (n2nmn_grad_layout: variable i at
+ * [offset_i, offset_i + numel_i), reference element order).  m / v: device, n2nmn_grad_numel floats
+ * each; either may be NULL (both: N2NMN_EINVAL).  Device-to-device copies on `stream`, ordered behind an
+ * earlier n2nmn_adam_step like n2nmn_train_reset_optimizer.  Root context with training enabled only.
+ * The step count is the caller's (n2nmn_adam_step takes it), so it is the caller's to save. */
+int n2nmn_train_get_moments(n2nmn_ctx *ctx, float *m_out, float *v_out, n2nmn_stream stream);
+int n2nmn_train_set_moments(n2nmn_ctx *ctx, const float *m, const float *v, n2nmn_stream stream);
 /* copies variable `name` (current value, reference layout) into `out` (device) */
 int n2nmn_get_weight(n2nmn_ctx *ctx, const char *name, float *out, n2nmn_stream stream);
 /* debug / parity: copy an internal gradient tensor ("d_word_vecs" [T_dec,N,E], "d_token_scores"

@@ -131,6 +131,8 @@ SYMBOLS = [
                              C.c_float, C.c_int64, _P]),
     ('n2nmn_dropout_multipliers', _I, [_P, C.c_int64, C.c_float, C.c_uint64, C.c_uint64, _P]),
     ('n2nmn_train_reset_optimizer', _I, [_P, _P]),
+    ('n2nmn_train_get_moments', _I, [_P, _P, _P, _P]),
+    ('n2nmn_train_set_moments', _I, [_P, _P, _P, _P]),
     ('n2nmn_get_weight', _I, [_P, C.c_char_p, _P, _P]),
     ('n2nmn_train_debug_tensor', C.c_int64, [_P, C.c_char_p, _P, C.c_int64, _P]),
     ('n2nmn_comm_unique_id', _I, [_P]),

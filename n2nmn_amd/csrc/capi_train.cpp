@@ -1295,6 +1295,35 @@ int n2nmn_train_reset_optimizer(n2nmn_ctx* c, n2nmn_stream stream) {
   return N2NMN_OK;
 }
 
+// The moments are already flat in the gradient's layout (n2nmn_train_enable: var_off), so saving and
+// restoring them is one device-to-device copy each, ordered like the memsets above: behind the late half
+// of a previous Adam update on the side stream, and on the caller's stream.
+int n2nmn_train_get_moments(n2nmn_ctx* c, float* m_out, float* v_out, n2nmn_stream stream) {
+  N2_REQUIRE(c, N2NMN_EINVAL, "train_get_moments: null context");
+  N2_REQUIRE(!c->parent, N2NMN_EINVAL, "train_get_moments: the optimiser lives on the root context, not on a fork");
+  N2_REQUIRE(c->train, N2NMN_EINVAL, "train_get_moments: training not enabled");
+  N2_REQUIRE(m_out || v_out, N2NMN_EINVAL, "train_get_moments: both m_out and v_out are NULL");
+  TrainState* t = c->train;
+  const size_t bytes = sizeof(float) * (size_t)t->total;
+  t->join(S(stream));
+  if (m_out) N2_HIP(hipMemcpyAsync(m_out, t->m, bytes, hipMemcpyDeviceToDevice, S(stream)));
+  if (v_out) N2_HIP(hipMemcpyAsync(v_out, t->v, bytes, hipMemcpyDeviceToDevice, S(stream)));
+  return N2NMN_OK;
+}
+
+int n2nmn_train_set_moments(n2nmn_ctx* c, const float* m, const float* v, n2nmn_stream stream) {
+  N2_REQUIRE(c, N2NMN_EINVAL, "train_set_moments: null context");
+  N2_REQUIRE(!c->parent, N2NMN_EINVAL, "train_set_moments: the optimiser lives on the root context, not on a fork");
+  N2_REQUIRE(c->train, N2NMN_EINVAL, "train_set_moments: training not enabled");
+  N2_REQUIRE(m || v, N2NMN_EINVAL, "train_set_moments: both m and v are NULL");
+  TrainState* t = c->train;
+  const size_t bytes = sizeof(float) * (size_t)t->total;
+  t->join(S(stream));
+  if (m) N2_HIP(hipMemcpyAsync(t->m, m, bytes, hipMemcpyDeviceToDevice, S(stream)));
+  if (v) N2_HIP(hipMemcpyAsync(t->v, v, bytes, hipMemcpyDeviceToDevice, S(stream)));
+  return N2NMN_OK;
+}
+
 int n2nmn_debug_gemm_tn(n2nmn_ctx* ctx, const float* A, int lda, int M, const float* B, int ldb,
                         int N, int R, float* C, int ldc, const int32_t* a_row_idx,
                         const int32_t* a_onehot, const int32_t* b_sel, int b_sel_val,

@@ -341,6 +341,10 @@ class ShapesTrainer(Trainer):
             raise KeyError('models_shapes variables: missing %s, unknown %s' % (missing[:4], extra[:4]))
         self.engine.load_weights({inv[k]: v for k, v in weights.items()})
 
+    def _state_variables(self):
+        """optimizer_state() / load_optimizer_state() use the models_shapes names too"""
+        return {k: (reference_name(k), tuple(shape)) for k, (_, _, shape) in self.layout.items()}
+
 
 __all__ = ['Assembler', 'NMN3ModelAtt', 'SHAPES_MODULE_NAMES', 'ShapesTrainer', 'shapes_engine', 'shapes_dims',
            'reference_name', 'shapes_engine_variable_shapes', 'l2_variables']

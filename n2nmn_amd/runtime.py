@@ -213,16 +213,56 @@ def register_model(model):
 _SEED = [0]            # tf.set_random_seed(seed): seeds global_variables_initializer's draws
 
 
+_SAVE_OPTIMIZER_STATE = [False]
+
+
+def save_optimizer_state(on: bool = True) -> bool:
+    """Module-level switch, set once beside the import table that hands a driver this `tf`: Saver.save also
+    writes the optimiser state of every model's trainer (Trainer.optimizer_state: Adam's slots, the beta powers,
+    the step count, the dropout stream's offset), so a later run can continue from the snapshot.  Off by
+    default: a snapshot then holds the variables alone.  Returns the previous setting."""
+    was = _SAVE_OPTIMIZER_STATE[0]
+    _SAVE_OPTIMIZER_STATE[0] = bool(on)
+    return was
+
+
+def _optimizer_entries(model, tensors):
+    """the entries of `tensors` that are optimiser state of `model` ({} unless a slot of one of its variables is
+    among them: the beta powers alone say nothing)"""
+    from .train import is_optimizer_state_key
+    shapes = getattr(model, 'variable_shapes', None)
+    names = set(shapes()) if shapes is not None else set()
+    found = {k: v for k, v in tensors.items() if is_optimizer_state_key(k, names)}
+    return found if any(k.endswith(('/Adam', '/Adam_1')) for k in found) else {}
+
+
+def attach_trainer(model, trainer):
+    """runtime_train.TrainStep.ensure_trainer: `trainer` now trains `model`.  Optimiser state that a
+    Saver.restore found before the trainer existed is applied here, after the constructor's reset."""
+    model._trainer = trainer
+    pending = getattr(model, '_pending_optimizer_state', None)
+    if pending:
+        model._pending_optimizer_state = None
+        trainer.load_optimizer_state(pending, strict=False)
+
+
 class _Saver:
     """tf.train.Saver: restore(sess, path) loads reference-named variables into every model built
     so far -- from `path`.npz / `path` (an .npz of name -> array) or a TensorFlow V2 checkpoint
-    prefix (n2nmn_amd.tf_checkpoint); save(sess, path) writes a TensorFlow V2 checkpoint of the models'
-    variables (and the script's own tf.Variables) under their reference names."""
+    prefix (n2nmn_amd.tf_checkpoint) -- and, where the file holds them, Adam's slots into the model's trainer;
+    save(sess, path) writes a TensorFlow V2 checkpoint of the models' variables (and the script's own
+    tf.Variables) under their reference names, with the optimiser state under save_optimizer_state(True)."""
 
     def __init__(self, var_list=None, *args, **kwargs):
         self.var_list = list(var_list) if var_list is not None else None
 
     def restore(self, sess, path):
+        """The optimiser entries of the file (`<name>/Adam`, `<name>/Adam_1`, the beta powers, this package's step
+        count and dropout offset) go to the model's trainer -- at once if it exists, else when the first fetched
+        `train_step` creates it -- whatever `var_list` names: the fine-tuning scripts restore
+        `[v for v in tf.global_variables() if v != baseline]` AFTER building their optimiser
+        (train_clevr_rl_gt_layout.py:132-139,178-179), so tf.global_variables() includes the slots and Adam
+        continues from the cloning run; only `baseline` starts fresh.  A file without slots loads as before."""
         import os
         if os.path.exists(path + '.npz') or path.endswith('.npz'):
             z = np.load(path if path.endswith('.npz') else path + '.npz')
@@ -233,25 +273,44 @@ class _Saver:
         if not _MODELS:
             raise RuntimeError('Saver.restore: no model has been built')
         for m in _MODELS:
-            m.load_weights(weights)
+            state = _optimizer_entries(m, weights)
+            if not state:
+                m.load_weights(weights)
+                continue
+            m.load_weights({k: v for k, v in weights.items() if k not in state})
+            trainer = getattr(m, '_trainer', None)
+            if trainer is not None:
+                trainer.load_optimizer_state(state, strict=False)
+            else:
+                m._pending_optimizer_state = state
 
     def save(self, sess, path, global_step=None, write_meta_graph=True, **kwargs):
         """`<path>.index` + `<path>.data-00000-of-00001` (train_clevr_gt_layout.py:221-223).  Stored: every
         variable of every model built so far (float32, reference names) and the script's tf.Variables.
-        NOT stored: the Adam slot variables TensorFlow's Saver would add (`<name>/Adam`, `<name>/Adam_1`,
-        `beta1_power`, `beta2_power`) -- the optimiser state stays inside the library; the reference's eval
-        and fine-tuning scripts restore model variables only (train_clevr_rl_gt_layout.py:168-169)."""
+        The Adam variables TensorFlow's Saver would add (`<name>/Adam`, `<name>/Adam_1`, `beta1_power`,
+        `beta2_power`) are stored only under save_optimizer_state(True), from each model's trainer
+        (Trainer.optimizer_state); a `var_list` then passes a variable's slots along with it.  The reference's
+        fine-tuning scripts do restore them: train_clevr_rl_gt_layout.py:178-179 restores every global variable
+        but `baseline` after the optimiser has been built (:132-139), slots and beta powers included."""
         from . import tf_checkpoint
+        from .train import is_optimizer_state_key
         if global_step is not None:
             path = '%s-%d' % (path, int(global_step))
         tensors = {}
+        state = {}
         for m in _MODELS:
             tensors.update({k: to_numpy(v) for k, v in m.get_weights().items()})
+            if _SAVE_OPTIMIZER_STATE[0]:
+                trainer = getattr(m, '_trainer', None)
+                state.update(trainer.optimizer_state() if trainer is not None else
+                             (getattr(m, '_pending_optimizer_state', None) or {}))
         for v in _rt._GLOBALS:
             tensors[v.name] = np.asarray(v.read(), np.float32)
         if self.var_list is not None:
             keep = {getattr(v, 'name', None) for v in self.var_list}
             tensors = {k: v for k, v in tensors.items() if k in keep}
+            state = {k: v for k, v in state.items() if is_optimizer_state_key(k, keep)}
+        tensors.update(state)
         tf_checkpoint.write_checkpoint(path, tensors)
         return path
 

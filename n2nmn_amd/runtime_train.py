@@ -487,6 +487,10 @@ class TrainStep:
                                        baseline_decay=self.baseline_decay)
                 self.trainer.set_baseline(float(plan.baseline.read()))
                 plan.baseline._reader = self.trainer.get_baseline
+            # optimiser state a Saver.restore found before this trainer existed (the fine-tuning scripts restore
+            # right after building the graph) goes in now, behind the constructor's reset
+            from .runtime import attach_trainer
+            attach_trainer(self.model, self.trainer)
         return self.trainer
 
     def run(self, handle):

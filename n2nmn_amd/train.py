@@ -29,6 +29,80 @@ BWD_DEFER_JOIN = 0x10          # include/n2nmn.h
 DROPOUT_FIELDS = dict(enc0='drop_enc0', dec0='drop_dec0', qpn_h='drop_qpn_h', qpn_fc1='drop_qpn_fc1')
 
 
+# ---- optimiser state: the names a TensorFlow 1.0.0 Saver gives Adam's variables (restated from
+# tensorflow/python/training/adam.py and slot_creator.py: slots `<variable>/Adam` = m and `<variable>/Adam_1` = v,
+# non-slot `beta1_power` / `beta2_power` that START at beta and are multiplied by beta after every step), plus
+# two entries of this package's own for what TensorFlow keeps nowhere a Saver reaches
+ADAM_STEP_KEY = 'n2nmn_amd/adam_step'
+DROPOUT_OFFSET_KEY = 'n2nmn_amd/dropout_offset'
+_SCALAR_KEYS = ('beta1_power', 'beta2_power', ADAM_STEP_KEY, DROPOUT_OFFSET_KEY)
+
+
+def slot_names(variable: str):
+    """(first moment, second moment) entries of one variable"""
+    return variable + '/Adam', variable + '/Adam_1'
+
+
+def optimizer_state_keys(variables) -> list:
+    """every key of Trainer.optimizer_state() for reference-named `variables`, in its order"""
+    return [s for v in variables for s in slot_names(v)] + list(_SCALAR_KEYS)
+
+
+def is_optimizer_state_key(key: str, variables) -> bool:
+    """`key` is an optimiser entry of a model whose variables are `variables` (a set)"""
+    if key in _SCALAR_KEYS:
+        return True
+    for suffix in ('/Adam', '/Adam_1'):
+        if key.endswith(suffix) and key[:-len(suffix)] in variables:
+            return True
+    return False
+
+
+def beta_powers(iteration: int, beta1: float, beta2: float):
+    """(beta1_power, beta2_power) after `iteration` steps, float32: beta ** (iteration + 1) of the float32 beta
+    the update itself uses (TensorFlow holds both as float32 variables)."""
+    t = int(iteration) + 1
+    return tuple(np.float32(float(np.float32(b)) ** t) for b in (beta1, beta2))
+
+
+def step_drift_bound(iteration: int, beta2: float) -> int:
+    """How many steps iteration_from_state() may be off for a `beta2_power` that TensorFlow accumulated as a
+    float32 product (derivation there): ceil(iteration * 2^-24 / |ln beta2|) once that exceeds 1/2, else 0."""
+    d = int(iteration) * 2.0 ** -24 / abs(np.log(float(np.float32(beta2))))
+    return 0 if d < 0.5 else int(np.ceil(d))
+
+
+def iteration_from_state(state, beta2: float) -> int:
+    """The number of steps taken, from an optimiser state: its ADAM_STEP_KEY entry when it has one (files this
+    package wrote), else round(log(beta2_power) / log(beta2)) - 1 (files TensorFlow wrote).  beta1_power is
+    never used: at 0.9 it leaves float32's range after roughly 900 steps.
+
+    The second form is exact for short runs and APPROXIMATE for long ones.  TensorFlow's beta2_power is
+    fl(beta2) times itself t more times in float32, every product rounded with relative error <= u = 2^-24,
+    so it equals beta2^(t+1) * prod(1 + e_i) with |e_i| <= u and the recovered exponent is off by at most
+    t * u / |ln beta2| steps.  At beta2 = 0.999 that is t * 5.96e-5: below 1/2, i.e. rounded away, for every
+    t < 8393, and at most 5 steps at t = 80000 (step_drift_bound).  It is harmless there because the step count
+    enters the update only through lr_t / lr = sqrt(1 - beta2^t) / (1 - beta1^t): a drift of d steps changes
+    beta2^t by the factor beta2^d, so the square root moves by about beta2^t * d * |ln beta2| / 2
+    <= beta2^t * t * u / 2.  With t * beta2^t <= 1 / (e * |ln beta2|) = 368 that is never more than 1.1e-5
+    relative (reached near t = 1000, where d rounds to zero anyway).  Where d can be nonzero (t >= 8393) the
+    bound beta2^t * t * u / 2 is 5.7e-8 already, under float32's resolution u, and falls off as e^(-t/1000):
+    at t = 80000 beta2^t = 1.7e-35 and the factor differs from 1 by about 4e-38 whatever d is; beta1^t
+    underflowed long before.  A beta2_power that has underflowed to zero (t beyond ~103 000) gives the first
+    step count at which float32 does so; the same argument covers it."""
+    if ADAM_STEP_KEY in state:
+        return int(np.asarray(state[ADAM_STEP_KEY]).reshape(-1)[0])
+    if 'beta2_power' not in state:
+        raise KeyError('optimizer state: neither %s nor beta2_power' % ADAM_STEP_KEY)
+    b2p = float(np.asarray(state['beta2_power'], np.float64).reshape(-1)[0])
+    lb = np.log(float(np.float32(beta2)))
+    if not (b2p < 1.0) or lb >= 0.0:
+        raise ValueError('optimizer state: beta2_power %r is not a power of beta2 = %r' % (b2p, beta2))
+    if b2p <= 0.0:
+        return int(np.ceil(np.log(2.0 ** -150) / lb))
+    return max(int(round(np.log(b2p) / lb)) - 1, 0)
+
+
 class DropoutStream:
     """Dropout multipliers (0 or 1 / keep_prob per element) of one model: from {0, 1} keep masks, or drawn
     on the device from the library's counter-based stream at (seed, offset), each draw taking a fresh
@@ -391,6 +465,86 @@ class Trainer:
                                                   self.engine.stream()))
             out[name] = t
         return out
+
+    # -- optimiser state ---------------------------------------------------------------------------
+    def _state_variables(self) -> Dict[str, tuple]:
+        """engine variable name -> (reference name, reference shape) of its optimiser entries"""
+        return {name: (name, tuple(shape)) for name, (_, _, shape) in self.layout.items()}
+
+    def _state_to_reference(self, name: str, a: np.ndarray) -> np.ndarray:
+        """engine-shaped moment of engine variable `name` -> reference shape (identity unless the context pads)"""
+        return a
+
+    def _state_from_reference(self, name: str, a: np.ndarray) -> np.ndarray:
+        return a
+
+    def _read_moments(self):
+        """(m, v): host copies of the flat moment vectors"""
+        torch = _torch()
+        e = self.engine
+        m = torch.empty(self.numel, dtype=torch.float32, device=e.device)
+        v = torch.empty(self.numel, dtype=torch.float32, device=e.device)
+        _lib.check(self._lib.n2nmn_train_get_moments(self._ctx, m.data_ptr(), v.data_ptr(), e.stream()))
+        torch.cuda.synchronize(e.device)
+        return m.cpu().numpy(), v.cpu().numpy()
+
+    def _write_moments(self, m: np.ndarray, v: np.ndarray):
+        torch = _torch()
+        e = self.engine
+        md = torch.as_tensor(m).to(device=e.device, dtype=torch.float32).contiguous()
+        vd = torch.as_tensor(v).to(device=e.device, dtype=torch.float32).contiguous()
+        _lib.check(self._lib.n2nmn_train_set_moments(self._ctx, md.data_ptr(), vd.data_ptr(), e.stream()))
+        torch.cuda.synchronize(e.device)     # (md / vd live until the copies are done)
+
+    def optimizer_state(self) -> Dict[str, np.ndarray]:
+        """What a TensorFlow 1.0.0 Saver stores for tf.train.AdamOptimizer besides the variables, as host arrays
+        (the keys of optimizer_state_keys): `<name>/Adam` (m) and `<name>/Adam_1` (v) per variable, reference-named
+        and reference-shaped float32; `beta1_power` / `beta2_power` = beta ** (iteration + 1), float32 scalars;
+        and, int64 scalars of this package's own, the step count and the dropout stream's offset.  The REINFORCE
+        `baseline` is not part of it (the reference's fine-tuning scripts leave it out of what they restore,
+        train_clevr_rl_gt_layout.py:178-179): get_baseline / set_baseline."""
+        m, v = self._read_moments()
+        out: Dict[str, np.ndarray] = {}
+        for name, (ref, _) in self._state_variables().items():
+            off, n, shape = self.layout[name]
+            km, kv = slot_names(ref)
+            out[km] = np.ascontiguousarray(self._state_to_reference(name, m[off:off + n].reshape(shape)), np.float32)
+            out[kv] = np.ascontiguousarray(self._state_to_reference(name, v[off:off + n].reshape(shape)), np.float32)
+        out['beta1_power'], out['beta2_power'] = beta_powers(self.iteration, self.hyper['beta1'], self.hyper['beta2'])
+        out[ADAM_STEP_KEY] = np.int64(self.iteration)
+        out[DROPOUT_OFFSET_KEY] = np.int64(self.dropout_stream.offset)
+        return out
+
+    def load_optimizer_state(self, state, strict: bool = True):
+        """Inverse of optimizer_state(): sets the moments, `iteration` (iteration_from_state: the stored step
+        count, else recovered from beta2_power -- approximate for long runs, see there) and, where present, the
+        dropout stream's offset.  strict=False leaves the moments of a variable at zero when BOTH its entries
+        are absent and, without any step entry, the iteration as it is; entries of other names are ignored.
+        A wrong-shaped entry raises ValueError naming the variable."""
+        m = np.zeros(self.numel, np.float32)
+        v = np.zeros(self.numel, np.float32)
+        for name, (ref, ref_shape) in self._state_variables().items():
+            off, n, shape = self.layout[name]
+            keys = slot_names(ref)
+            have = [k in state for k in keys]
+            if not any(have) and not strict:
+                continue
+            if not all(have):
+                raise KeyError('optimizer state: no entry %s' % keys[have.index(False)])
+            for k, flat in zip(keys, (m, v)):
+                a = np.asarray(state[k], np.float32)
+                if tuple(a.shape) != ref_shape:
+                    raise ValueError('optimizer state %s: shape %s, the variable %s is %s'
+                                     % (k, tuple(a.shape), ref, ref_shape))
+                flat[off:off + n] = np.asarray(self._state_from_reference(name, a), np.float32).reshape(-1)
+        if strict or ADAM_STEP_KEY in state or 'beta2_power' in state:
+            iteration = iteration_from_state(state, self.hyper['beta2'])
+        else:
+            iteration = self.iteration
+        self._write_moments(m, v)
+        self.iteration = iteration
+        if DROPOUT_OFFSET_KEY in state:
+            self.dropout_stream.offset = int(np.asarray(state[DROPOUT_OFFSET_KEY]).reshape(-1)[0])
 
     def debug_tensor(self, name: str, shape):
         torch = _torch()

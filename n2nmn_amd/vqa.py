@@ -372,3 +372,15 @@ class VQATrainer(Trainer):
     def weights_reference_shaped(self):
         d, di = self.vqa.dims, self.vqa.idims
         return {k: unpad_variable(k, v.cpu().numpy(), d, di) for k, v in self.get_weights().items()}
+
+    # optimizer_state() / load_optimizer_state(): reference-shaped moments.  A padding element's gradient is
+    # zero at every step, so its moments are zero forever: dropped on the way out, zero on the way in.
+    def _state_variables(self):
+        shapes = vqa_variable_shapes(self.vqa.dims)
+        return {name: (name, tuple(shapes[name])) for name in self.layout}
+
+    def _state_to_reference(self, name, a):
+        return unpad_variable(name, a, self.vqa.dims, self.vqa.idims)
+
+    def _state_from_reference(self, name, a):
+        return pad_variable(name, a, self.vqa.dims, self.vqa.idims)
