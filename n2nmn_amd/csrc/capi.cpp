@@ -365,6 +365,24 @@ static void attach_planes(const n2nmn_ctx* c, LstmJob& j) {
           j.Wp64 == c->dec_W0h_64 ? c->dec_W0h_b3 : j.Wp64 == c->dec_W1_64 ? c->dec_W1_b3 : nullptr;
 }
 
+// The kernel of a recurrent step launch over N rows.  wide: lstm_wide's choice, or 1 where the caller
+// knows that few rows are left (tile_min_rows).  A split-operand pass (lstm_b3) runs lstm_tile3_kernel
+// while wide != 1 and the exact-fp32 K-split tiles for its tail, which write the bf16 planes of what they
+// produce; every other pass is launch_lstm_step's choice.
+static int lstm_step_route(const n2nmn_ctx* c, LstmJob* jobs, int njobs, int N, int L, int rows_per_wg, int wide,
+                           const char* who, hipStream_t s) {
+  if (lstm_b3(c, N)) {
+    for (int i = 0; i < njobs; ++i) attach_planes(c, jobs[i]);
+    if (wide != 1) {
+      N2_REQUIRE(lstm_tile3_supported(jobs, njobs, L), N2NMN_EINVAL, std::string(who) + ": bf16x3 mode: unsupported job");
+      launch_lstm_tile3(jobs, njobs, N, L, s);
+      return N2NMN_OK;
+    }
+  }
+  launch_lstm_step(jobs, njobs, N, L, rows_per_wg, s, wide);
+  return N2NMN_OK;
+}
+
 void packed_state(const n2nmn_ctx* c, LstmJob& j) {
   j.a_rs = 4; j.a_ks = 4 * c->d.N; j.hp_R = c->d.N;
 }
@@ -515,17 +533,7 @@ int encoder_impl(n2nmn_ctx* c, const n2nmn_seq2seq_io* io, hipStream_t s, GemmAr
       ProfScope ps(c, F_LSTM_ENC, fl, by, s);
       int wide = lstm_wide(c);
       if (!act_host.empty() && act_host[std::min(k, T - 1)] <= tile_min_rows(c)) wide = 1;
-      if (b3) {
-        attach_planes(c, j0); attach_planes(c, j1);
-        if (wide == 1) {              // tail of the length-sorted encoder: exact-fp32 K-split tiles (+ planes)
-          launch_lstm_step(jobs, 2, N, L, 64, s, 1);
-        } else {
-          N2_REQUIRE(lstm_tile3_supported(jobs, 2, L), N2NMN_EINVAL, "encoder_forward: bf16x3 mode: unsupported job");
-          launch_lstm_tile3(jobs, 2, N, L, s);
-        }
-      } else {
-        launch_lstm_step(jobs, 2, N, L, 64, s, wide);
-      }
+      if (const int rc = lstm_step_route(c, jobs, 2, N, L, 64, wide, "encoder_forward", s)) return rc;
     }
   }
   // encoder_h_transformed = fc(encoder_outputs)          (nmn3_netgen_att.py:102-106)
@@ -719,17 +727,7 @@ int decoder_impl(n2nmn_ctx* c, const n2nmn_seq2seq_io* io, hipStream_t s, const 
       ProfScope ps(c, F_LSTM_DEC0, (j0.active ? fl0 * live0 / N : 0) + (j1.active ? fl1 * live1 / N : 0),
                    (j0.active ? 4.0 * ((double)L * 4 * L + 3.0 * live0 * L) : 0) +
                    (j1.active ? 4.0 * (2.0 * L * 4 * L + 5.0 * live1 * L) : 0), s);
-      if (lstm_b3(c, N)) {
-        attach_planes(c, j0); attach_planes(c, j1);
-        if (wide == 1) {              // (exact-fp32 K-split tiles; they write the planes of what they produce)
-          launch_lstm_step(jobs, 2, N, L, 64, s, 1);
-        } else {
-          N2_REQUIRE(lstm_tile3_supported(jobs, 2, L), N2NMN_EINVAL, "decoder_forward: bf16x3 mode: unsupported job");
-          launch_lstm_tile3(jobs, 2, N, L, s);
-        }
-      } else {
-        launch_lstm_step(jobs, 2, N, L, 64, s, wide);
-      }
+      if (const int rc = lstm_step_route(c, jobs, 2, N, L, 64, wide, "decoder_forward", s)) return rc;
     }
     // q = out . W_a + b_a for all steps (nmn3_netgen_att.py:185), in ONE launch with whatever else
     // is due before the attention / the layout walk: encoder_h_transform, conv_image
@@ -890,13 +888,7 @@ int decoder_impl(n2nmn_ctx* c, const n2nmn_seq2seq_io* io, hipStream_t s, const 
         ProfScope ps(c, F_LSTM_DEC0, fl0 * live / N, 4.0 * ((double)L * 4 * L + 3.0 * live * L), s);
         // (throughput mode, >= 128 rows: the 64 x 64 LDS-DMA tiles, one round of 512 workgroups per
         // layer -- the greedy decoder's two layers cannot share a launch, token t feeds layer 0 of t+1)
-        if (lstm_b3(c, N)) {
-          attach_planes(c, j0);
-          N2_REQUIRE(lstm_tile3_supported(&j0, 1, L), N2NMN_EINVAL, "decoder_forward: bf16x3 mode: unsupported job");
-          launch_lstm_tile3(&j0, 1, N, L, s);
-        } else {
-          launch_lstm_step(&j0, 1, N, L, 32, s, lstm_wide(c));
-        }
+        if (const int rc = lstm_step_route(c, &j0, 1, N, L, 32, lstm_wide(c), "decoder_forward", s)) return rc;
       }
       LstmJob j1{};
       j1.active = 1;
@@ -915,13 +907,7 @@ int decoder_impl(n2nmn_ctx* c, const n2nmn_seq2seq_io* io, hipStream_t s, const 
       j1.perm = live_perm; j1.n_active = live_n;
       {
         ProfScope ps(c, F_LSTM_DEC1, fl1 * live / N, 4.0 * (2.0 * L * 4 * L + 5.0 * live * L), s);
-        if (lstm_b3(c, N)) {
-          attach_planes(c, j1);
-          N2_REQUIRE(lstm_tile3_supported(&j1, 1, L), N2NMN_EINVAL, "decoder_forward: bf16x3 mode: unsupported job");
-          launch_lstm_tile3(&j1, 1, N, L, s);
-        } else {
-          launch_lstm_step(&j1, 1, N, L, 32, s, lstm_wide(c));
-        }
+        if (const int rc = lstm_step_route(c, &j1, 1, N, L, 32, lstm_wide(c), "decoder_forward", s)) return rc;
       }
       LstmJob jq{};                    // q = out . W_a + b_a            (nmn3_netgen_att.py:185)
       packed_state(c, jq);

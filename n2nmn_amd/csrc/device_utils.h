@@ -104,6 +104,28 @@ __device__ __forceinline__ float block_reduce(float v, float* scratch) {
   return r;
 }
 
+// One LDS-DMA instruction: every lane copies 16 bytes from `base + voff` to LDS[lds + 16 * lane]
+// (global_load_lds_dwordx4; M0 carries the LDS address).  M0 is compiler-reserved, so it is saved and
+// restored inside the statement (cdna_hip_programming.md 5.7).  hipcc does not count this load: the
+// waits are ours (wait_vm).
+__device__ __forceinline__ void glds16(const void* base, uint32_t voff, uint32_t lds) {
+  uint32_t keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\t"
+      "s_mov_b32 m0, %3\n\t"
+      "s_nop 0\n\t"
+      "global_load_lds_dwordx4 %1, %2\n\t"
+      "s_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(voff), "s"(base), "s"(lds)
+      : "memory");
+}
+// until at most N of this wave's vector-memory operations (LDS-DMA included) are outstanding
+template <int N>
+__device__ __forceinline__ void wait_vm() {
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // tanh / sigmoid on the hardware transcendentals: v_exp_f32 (2^x) and v_rcp_f32 (1 ulp).

@@ -123,8 +123,9 @@ struct LstmJob {
   // their length (whole 16-row tiles beyond it skip their loads and MFMAs)
   const int32_t* perm;    // [N] or nullptr (identity)
   const int32_t* n_active;// device scalar for this step or nullptr (= N)
-  float* fin_c;           // [N][L] row-major, ORIGINAL order: c of a row at the step it finishes
-  float* fin_h;           // k-interleaved [L/4][R][4], ORIGINAL order (or nullptr)
+  float* fin_c;           // k-interleaved [L/4][R][4] (R = hp_R), ORIGINAL order: c of a row at the step it
+                          // finishes (or nullptr)
+  float* fin_h;           // its h, same layout (or nullptr)
   int active;             // 0: skip this job entirely (pipeline fill / drain)
   // training: activations kept for the backward pass (ORIGINAL row order), or nullptr
   float4* save_gates;     // [N][L] (i, j, f, o) after their nonlinearities, this step

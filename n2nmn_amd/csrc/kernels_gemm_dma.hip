@@ -37,19 +37,6 @@ constexpr int DMA_THREADS = 512;
 constexpr int DSTAGE = (DM * DK + DK * DN) * 4;          // 32 KiB: A image 16 KiB, then B image
 constexpr int DB_IMAGE = DM * DK * 4;
 
-__device__ __forceinline__ void glds16(const float* base, uint32_t voff, uint32_t lds) {
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %3\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, %2\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(voff), "s"(base), "s"(lds)
-      : "memory");
-}
-
 struct Frag { float4 a; float4 b[2]; };
 
 __device__ __forceinline__ void gemm_dma_body(const GemmArgs& a, const int bx, const int by) {
@@ -146,7 +133,7 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& a, const int bx, c
   for (int s = 0; s < nst; ++s) {
     // this wave's pieces of stage s have landed; after the barrier everyone's have, and everyone is
     // done reading stage s - 1, whose buffer the DMA of stage s + 1 refills under this stage's MFMAs
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     __builtin_amdgcn_s_barrier();
     if (s + 1 < nst) issue(s + 1);
     Frag P = read_frag(s, 0);

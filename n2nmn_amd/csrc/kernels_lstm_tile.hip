@@ -24,16 +24,13 @@
 //     q = l / 16) ends up holding z of units 4q .. 4q+3 of ONE row for all four gates: the cell
 //     update is register-local and c / h are read and written as the float4 elements of the
 //     k-interleaved state layout ([L/4][R][4]), 256 contiguous bytes per 16 lanes.
-// Grid: flat; id -> (job, row block, column tile) with the column tile fastest, so that tile % 8 is
-// the XCD of the workgroup: an XCD's L2 keeps ITS eighth of the weights across the steps of a pass
-// and only h (new every step) comes over the fabric.  The layer-1 job (K = 2L) goes first: with two
-// workgroups per CU every CU gets one K = 2L and one K = L tile.  (Equal-size work items -- the
-// K = 2L tile as two workgroups that meet through L2 -- were built and measured:
-// tools/rejected/lstm_tile_equal_items.hip.txt; the hand-off costs what the balance gains.)
+// Grid: flat; id -> (job, row block, column tile) by lstm_tile_id (lstm_cell.h), which has the order and
+// its reasons.  (Equal-size work items -- the K = 2L tile as two workgroups that meet through L2 -- were
+// built and measured: tools/rejected/lstm_tile_equal_items.hip.txt; the hand-off costs what the balance
+// gains.)
 #include <type_traits>
 
-#include "device_utils.h"
-#include "kernels.h"
+#include "lstm_cell.h"
 
 namespace n2nmn {
 
@@ -45,92 +42,34 @@ constexpr int TILE_WAVES = 8, TILE_THREADS = TILE_WAVES * 64;
 constexpr int STAGE_BYTES = 2 * (TILE_BK / 4) * 64 * 16;      // h image 8 KiB, then W image 8 KiB
 constexpr int W_IMAGE = (TILE_BK / 4) * 64 * 16;
 
-struct LstmJobs2 {
-  LstmJob j[2];
-};
-
-// One LDS-DMA instruction: every lane copies 16 bytes from `base + voff` to LDS[lds + 16 * lane]
-// (global_load_lds_dwordx4; M0 carries the LDS address).  M0 is compiler-reserved, so it is saved and
-// restored inside the statement (cdna_hip_programming.md 5.7).  hipcc does not count this load: the
-// waits are ours.
-__device__ __forceinline__ void glds16(const float* base, uint32_t voff, uint32_t lds) {
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %3\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, %2\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(voff), "s"(base), "s"(lds)
-      : "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 // DBG (n2nmn_debug_lstm_bench only): 1 = no DMA (LDS holds whatever it held), 2 = no MFMA (operands
 // read from LDS and kept live), 3 = DMA + barriers only, 4 = no DMA waits in the k loop (wrong results),
 // 5 = every stage re-reads the first stage's (cache-hot) addresses
 template <int NS, int DBG = 0>
-__global__ __launch_bounds__(TILE_THREADS) void lstm_tile_kernel(LstmJobs2 jobs, int N, int L,
+__global__ __launch_bounds__(TILE_THREADS) void lstm_tile_kernel(LstmJobs jobs, int N, int L,
                                                                  int nrb, int njobs) {
   extern __shared__ __attribute__((aligned(1024))) char smem[];
   const int ntile = L / TILE_UNITS;
-  // ---- id -> (job, row block, column tile) -------------------------------------------------------
-  // Only row blocks with an active row do the step (length-sorted encoder: rows [nact, N) are past
-  // their length; the training step keeps every block).  Their workgroups take the ids
-  // [0, (nab1 + nab0) * ntile), the K = 2L job first, so the dispatcher spreads THEM over all CUs
-  // (with the blocks numbered in place, a half-active step ran two workgroups on half of the CUs);
-  // the ids behind write dynamic_rnn's zero output rows of the inactive blocks or leave.
-  int nab[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const LstmJob& jq = jobs.j[j];
-    int n = 0;
-    if (j < njobs && jq.active) {
-      const int na = (jq.n_active && !jq.save_gates) ? *jq.n_active : N;
-      n = (min(max(na, 0), N) + TILE_ROWS - 1) / TILE_ROWS;
-    }
-    nab[j] = n;
-  }
-  int rem = blockIdx.x / ntile;
-  const int ct = blockIdx.x - rem * ntile;
-  int jsel = -1, rb = 0;
-  bool zero_fill = false;
-#pragma unroll
-  for (int j = 1; j >= 0; --j)
-    if (jsel < 0) { if (rem < nab[j]) { jsel = j; rb = rem; } else rem -= nab[j]; }
-#pragma unroll
-  for (int j = 1; j >= 0; --j)
-    if (jsel < 0 && j < njobs && jobs.j[j].active && jobs.j[j].out_seq) {
-      if (rem < nrb - nab[j]) { jsel = j; rb = nab[j] + rem; zero_fill = true; } else rem -= nrb - nab[j];
-    }
-  if (jsel < 0) return;
-  const LstmJob& jb = jobs.j[jsel];
+  const LstmTileId id = lstm_tile_id<TILE_ROWS>(jobs, njobs, N, ntile, nrb);
+  if (id.job < 0) return;
+  const LstmJob& jb = jobs.j[id.job];
+  const int ct = id.ct;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = w & 3, kh = w >> 2;                // row group of the wave, and its half of every stage
-  const int row0 = rb * TILE_ROWS;
+  const int row0 = id.rb * TILE_ROWS;
   const int R = jb.hp_R;
-  const int nact = (jb.n_active && !jb.save_gates) ? *jb.n_active : N;
+  const int nact = lstm_tile_nact(jb, N);
 
   // ---- the lane's place in the epilogue: row lr of the wave, units 16 ct + 4 q .. + 3 ----------
   const int lr = lane & 15, q = lane >> 4;
   const int gr = row0 + 16 * wr + lr;
   const bool eact = gr < N;
   const int grc = eact ? gr : N - 1;
-  const int t4 = 4 * ct + q;                         // 4-unit group = float4 element of the state
-  if (zero_fill) {
-    // every row of the block is past its length: only dynamic_rnn's zero output row is left of the
-    // step (see lstm_step_kernel)
-    if (kh == 0 && eact) {
-      const int zr = jb.perm ? jb.perm[grc] : grc;
-      *reinterpret_cast<float4*>(jb.out_seq + (size_t)zr * L + 4 * t4) = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+  LstmCellAt at{grc, grc, 4 * ct + q, 0};           // 4-unit group = one float4 element of the state
+  if (id.zero_fill) {
+    if (kh == 0 && eact) lstm_zero_output<4>(jb, L, lstm_orow(jb, grc), at);
     return;
   }
 
@@ -169,25 +108,10 @@ __global__ __launch_bounds__(TILE_THREADS) void lstm_tile_kernel(LstmJobs2 jobs,
   // DMA prologue, used after the last MFMA.  (The compiler waits for its own loads with counts that
   // do not know about the DMAs: in the in-order queue that can only over-wait, here once at the
   // start, never in the k loop.) ---------------------------------------------------------------------
-  int orow = grc;
-  float4 add[4];
-  float4 c_old = make_float4(0.f, 0.f, 0.f, 0.f), h_prev = c_old;
-  bool masked = false;
-  const size_t sidx = ((size_t)t4 * R + grc) * 4;
+  LstmCellIn<4> in;
   if (kh == 0) {
-    if (jb.perm) orow = jb.perm[grc];                // original row of state row gr
-    const float* ar;
-    if (jb.xtab) {
-      const int xi = jb.xidx ? jb.xidx[orow] : jb.xidx_const;
-      ar = jb.xtab + (size_t)xi * 4 * L + 16 * t4;    // tile column order: [4-unit group][gate][unit]
-    } else {
-      ar = jb.bias + 16 * t4;
-    }
-#pragma unroll
-    for (int g = 0; g < 4; ++g) add[g] = *reinterpret_cast<const float4*>(ar + 4 * g);
-    c_old = *reinterpret_cast<const float4*>(jb.c_in + sidx);
-    masked = jb.seq_len && jb.t >= jb.seq_len[orow];      // dynamic_rnn past the length (A.2)
-    if (masked) h_prev = *reinterpret_cast<const float4*>(jb.h_old + sidx);
+    at.orow = lstm_orow(jb, grc);
+    lstm_cell_prefetch<4>(jb, L, at, in);
   }
 
   f32x4 acc[4];
@@ -301,47 +225,17 @@ __global__ __launch_bounds__(TILE_THREADS) void lstm_tile_kernel(LstmJobs2 jobs,
   }
 
   // ---- cell update: lane = (row, 4 units), acc[g][r] = z of gate g, unit 4q + r ------------------
-  float cn[4], hn[4], gi[4], gj[4], gf[4], go[4];
-  const float co[4] = {c_old.x, c_old.y, c_old.z, c_old.w};
+  float z[4][4];
 #pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const float zi = acc[0][r] + (r == 0 ? add[0].x : r == 1 ? add[0].y : r == 2 ? add[0].z : add[0].w);
-    const float zj = acc[1][r] + (r == 0 ? add[1].x : r == 1 ? add[1].y : r == 2 ? add[1].z : add[1].w);
-    const float zf = acc[2][r] + (r == 0 ? add[2].x : r == 1 ? add[2].y : r == 2 ? add[2].z : add[2].w);
-    const float zo = acc[3][r] + (r == 0 ? add[3].x : r == 1 ? add[3].y : r == 2 ? add[3].z : add[3].w);
-    gi[r] = fast_sigmoid(zi); gj[r] = fast_tanh(zj); gf[r] = fast_sigmoid(zf + 1.0f); go[r] = fast_sigmoid(zo);
-    cn[r] = co[r] * gf[r] + gi[r] * gj[r];
-    hn[r] = fast_tanh(cn[r]) * go[r];
-  }
-  float4 c4 = make_float4(cn[0], cn[1], cn[2], cn[3]);
-  float4 h4 = make_float4(hn[0], hn[1], hn[2], hn[3]);
-  float4 o4 = h4;
-  if (masked) { c4 = c_old; h4 = h_prev; o4 = make_float4(0.f, 0.f, 0.f, 0.f); }
-  *reinterpret_cast<float4*>(jb.c_out + sidx) = c4;
-  *reinterpret_cast<float4*>(jb.h_new + sidx) = h4;
-  const size_t oidx = (size_t)orow * L + 4 * t4;
-  if (jb.save_gates) {            // training: what the cell backward needs (ORIGINAL row order)
+  for (int g = 0; g < 4; ++g)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) jb.save_gates[oidx + r] = make_float4(gi[r], gj[r], gf[r], go[r]);
-    *reinterpret_cast<float4*>(jb.save_c + oidx) = c4;
-    *reinterpret_cast<float4*>(jb.save_h + oidx) = h4;
-  }
-  if (jb.out_seq) *reinterpret_cast<float4*>(jb.out_seq + oidx) = o4;
-  if (jb.h_drop) {                // dropped copy of the OUTPUT for the layer above (models_vqa)
-    const float4 dm = *reinterpret_cast<const float4*>(jb.drop + oidx);
-    const float4 hd = make_float4(h4.x * dm.x, h4.y * dm.y, h4.z * dm.z, h4.w * dm.w);
-    *reinterpret_cast<float4*>(jb.h_drop + sidx) = hd;
-    if (jb.save_hd) *reinterpret_cast<float4*>(jb.save_hd + oidx) = hd;
-  }
-  if (jb.fin_c && jb.seq_len && jb.t == jb.seq_len[orow] - 1) {   // the row's last valid step
-    const size_t fidx = ((size_t)t4 * R + orow) * 4;
-    *reinterpret_cast<float4*>(jb.fin_c + fidx) = c4;
-    *reinterpret_cast<float4*>(jb.fin_h + fidx) = h4;
-  }
+    for (int r = 0; r < 4; ++r) z[g][r] = acc[g][r];
+  lstm_add_last<4>(z, in);
+  lstm_cell_update<4, LSTM_OUT_SAVE>(jb, L, at, in, z);
 }
 
 template <int NS, int DBG = 0>
-void launch_tile(const LstmJobs2& js, int njobs, int N, int L, hipStream_t s) {
+void launch_tile(const LstmJobs& js, int njobs, int N, int L, hipStream_t s) {
   static std::atomic<uint64_t> attr{0};
   const int lds = NS * STAGE_BYTES;
   ensure_dynamic_lds(reinterpret_cast<const void*>(&lstm_tile_kernel<NS, DBG>), lds, attr);
@@ -365,11 +259,7 @@ bool lstm_tile_supported(const LstmJob* jobs, int njobs, int L) {
 }
 
 void launch_lstm_tile(const LstmJob* jobs, int njobs, int N, int L, int stages, hipStream_t s) {
-  LstmJobs2 js;
-  for (int i = 0; i < 2; ++i) {
-    if (i < njobs) js.j[i] = jobs[i];
-    else { js.j[i] = LstmJob{}; js.j[i].active = 0; }
-  }
+  const LstmJobs js = lstm_jobs(jobs, njobs);
   switch (stages) {
     case 3: launch_tile<3>(js, njobs, N, L, s); break;
     case 5: launch_tile<5>(js, njobs, N, L, s); break;

@@ -36,8 +36,7 @@
 // waves 0-3 run the register-local cell update.
 #include <type_traits>
 
-#include "device_utils.h"
-#include "kernels.h"
+#include "lstm_cell.h"
 
 namespace n2nmn {
 
@@ -57,83 +56,35 @@ template <int RG> struct T3 {
   static constexpr int PBASE = NPIECE / WAVES, PEXTRA = NPIECE % WAVES;   // per wave; waves < PEXTRA one more
 };
 
-struct LstmJobs3 {
-  LstmJob j[2];
-};
-
-__device__ __forceinline__ void glds16b(const void* base, uint32_t voff, uint32_t lds) {
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %3\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, %2\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(voff), "s"(base), "s"(lds)
-      : "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm3() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 // VAR (n2nmn_debug_lstm_bench only): 1 = no DMA, 2 = no MFMA, 3 = DMA + barriers only
 template <int NS, int RG, int VAR = 0>
-__global__ __launch_bounds__(T3<RG>::THREADS, RG == 4 ? 2 : 1) void lstm_tile3_kernel(LstmJobs3 jobs, int N,
+__global__ __launch_bounds__(T3<RG>::THREADS, RG == 4 ? 2 : 1) void lstm_tile3_kernel(LstmJobs jobs, int N,
                                                                                       int L, int nrb,
                                                                                       int njobs) {
   extern __shared__ __attribute__((aligned(1024))) char smem[];
   constexpr int T3_ROWS = T3<RG>::ROWS, T3_H_IMAGE = T3<RG>::H_IMAGE, T3_STAGE = T3<RG>::STAGE;
   constexpr int PMAX = T3<RG>::PBASE + (T3<RG>::PEXTRA ? 1 : 0);
   const int ntile = L / T3_UNITS;
-  // ---- id -> (job, row block, column tile): as lstm_tile_kernel (dense over the active row blocks,
-  // the K = 2L job first, column tile fastest so that tile % 8 is the workgroup's XCD)
-  int nab[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const LstmJob& jq = jobs.j[j];
-    int n = 0;
-    if (j < njobs && jq.active) {
-      const int na = jq.n_active ? *jq.n_active : N;
-      n = (min(max(na, 0), N) + T3_ROWS - 1) / T3_ROWS;
-    }
-    nab[j] = n;
-  }
-  int rem = blockIdx.x / ntile;
-  const int ct = blockIdx.x - rem * ntile;
-  int jsel = -1, rb = 0;
-  bool zero_fill = false;
-#pragma unroll
-  for (int j = 1; j >= 0; --j)
-    if (jsel < 0) { if (rem < nab[j]) { jsel = j; rb = rem; } else rem -= nab[j]; }
-#pragma unroll
-  for (int j = 1; j >= 0; --j)
-    if (jsel < 0 && j < njobs && jobs.j[j].active && jobs.j[j].out_seq) {
-      if (rem < nrb - nab[j]) { jsel = j; rb = nab[j] + rem; zero_fill = true; } else rem -= nrb - nab[j];
-    }
-  if (jsel < 0) return;
-  const LstmJob& jb = jobs.j[jsel];
+  const LstmTileId id = lstm_tile_id<T3_ROWS>(jobs, njobs, N, ntile, nrb);
+  if (id.job < 0) return;
+  const LstmJob& jb = jobs.j[id.job];
+  const int ct = id.ct;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = w % RG, gp = w / RG;               // row group of the wave, and its gate pair
-  const int row0 = rb * T3_ROWS;
+  const int row0 = id.rb * T3_ROWS;
   const int R = jb.hp_R;
-  const int nact = jb.n_active ? *jb.n_active : N;
+  const int nact = lstm_tile_nact(jb, N);
 
   // ---- the lane's place in the epilogue: row lr of the wave, units 16 ct + 4 q .. + 3 ----------
   const int lr = lane & 15, q = lane >> 4;
   const int gr = row0 + 16 * wr + lr;
   const bool eact = gr < N;
   const int grc = eact ? gr : N - 1;
-  const int t4 = 4 * ct + q;                         // 4-unit group = float4 element of the state
-  if (zero_fill) {
-    if (gp == 0 && eact) {
-      const int zr = jb.perm ? jb.perm[grc] : grc;
-      *reinterpret_cast<float4*>(jb.out_seq + (size_t)zr * L + 4 * t4) = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+  LstmCellAt at{grc, grc, 4 * ct + q, 0};           // 4-unit group = one float4 element of the state
+  if (id.zero_fill) {
+    if (gp == 0 && eact) lstm_zero_output<4>(jb, L, lstm_orow(jb, grc), at);
     return;
   }
 
@@ -175,8 +126,8 @@ __global__ __launch_bounds__(T3<RG>::THREADS, RG == 4 ? 2 : 1) void lstm_tile3_k
     const uint32_t sh = (uint32_t)(lo ? s : s - sL);
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
-      if (pish[i]) glds16b(lo ? A0p : A1p, pbase[i] + sh * pstep[i], slot + plds[i]);
-      else glds16b(Wp, pbase[i] + (uint32_t)s * pstep[i], slot + plds[i]);
+      if (pish[i]) glds16(lo ? A0p : A1p, pbase[i] + sh * pstep[i], slot + plds[i]);
+      else glds16(Wp, pbase[i] + (uint32_t)s * pstep[i], slot + plds[i]);
     }
   };
   // waves below PEXTRA issue one piece more per stage than the others: the counted waits differ, so
@@ -191,25 +142,10 @@ __global__ __launch_bounds__(T3<RG>::THREADS, RG == 4 ? 2 : 1) void lstm_tile3_k
   }
 
   // ---- epilogue operands (waves of gate pair 0 own the cell update): fetched under the DMA prologue
-  int orow = grc;
-  float4 add[4];
-  float4 c_old = make_float4(0.f, 0.f, 0.f, 0.f), h_prev = c_old;
-  bool masked = false;
-  const size_t sidx = ((size_t)t4 * R + grc) * 4;
+  LstmCellIn<4> in;
   if (gp == 0) {
-    if (jb.perm) orow = jb.perm[grc];                // original row of state row gr
-    const float* ar;
-    if (jb.xtab) {
-      const int xi = jb.xidx ? jb.xidx[orow] : jb.xidx_const;
-      ar = jb.xtab + (size_t)xi * 4 * L + 16 * t4;    // tile column order: [4-unit group][gate][unit]
-    } else {
-      ar = jb.bias + 16 * t4;
-    }
-#pragma unroll
-    for (int g = 0; g < 4; ++g) add[g] = *reinterpret_cast<const float4*>(ar + 4 * g);
-    c_old = *reinterpret_cast<const float4*>(jb.c_in + sidx);
-    masked = jb.seq_len && jb.t >= jb.seq_len[orow];      // dynamic_rnn past the length (A.2)
-    if (masked) h_prev = *reinterpret_cast<const float4*>(jb.h_old + sidx);
+    at.orow = lstm_orow(jb, grc);
+    lstm_cell_prefetch<4>(jb, L, at, in);
   }
 
   f32x4 acc[2];
@@ -255,8 +191,8 @@ __global__ __launch_bounds__(T3<RG>::THREADS, RG == 4 ? 2 : 1) void lstm_tile3_k
     constexpr int NP = decltype(np_tag)::value;
     auto sync_stage = [&](int next) {
       const int behind = nst - 1 - next;             // stages after `next`
-      if (behind >= NS - 3) wait_vm3<NP * (NS - 3)>();
-      else wait_vm3<0>();
+      if (behind >= NS - 3) wait_vm<NP * (NS - 3)>();
+      else wait_vm<0>();
       __builtin_amdgcn_s_barrier();
     };
     // One step: the 12 MFMAs of stage `cur` (in registers); woven in: the refill of the slot behind and
@@ -274,7 +210,7 @@ __global__ __launch_bounds__(T3<RG>::THREADS, RG == 4 ? 2 : 1) void lstm_tile3_k
         mma_gate(cur, 1);
       }
     };
-    wait_vm3<NP * (NS - 2)>();                     // stage 0 (the oldest of the NS - 1 in flight)
+    wait_vm<NP * (NS - 2)>();                     // stage 0 (the oldest of the NS - 1 in flight)
     __builtin_amdgcn_s_barrier();
     Grp P{}, Q{};
     if (WORK) fetch(P, 0);
@@ -306,47 +242,15 @@ __global__ __launch_bounds__(T3<RG>::THREADS, RG == 4 ? 2 : 1) void lstm_tile3_k
   }
   __syncthreads();
   if (gp == 1 || !eact) return;
-  const float4 zf4 = red[0], zo4 = red[64];
-  const float zfv[4] = {zf4.x, zf4.y, zf4.z, zf4.w}, zov[4] = {zo4.x, zo4.y, zo4.z, zo4.w};
 
-  // ---- cell update: lane = (row, 4 units), acc[g][r] = z of gate g, unit 4q + r ------------------
-  float cn[4], hn[4];
-  const float co[4] = {c_old.x, c_old.y, c_old.z, c_old.w};
+  // ---- cell update: lane = (row, 4 units); z of unit 4q + r: i, j in acc[0..1][r], f, o from LDS ----
+  float z[4][4];
+  ldw<4>(z[2], reinterpret_cast<const float*>(red));
+  ldw<4>(z[3], reinterpret_cast<const float*>(red + 64));
 #pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const float zi = acc[0][r] + (r == 0 ? add[0].x : r == 1 ? add[0].y : r == 2 ? add[0].z : add[0].w);
-    const float zj = acc[1][r] + (r == 0 ? add[1].x : r == 1 ? add[1].y : r == 2 ? add[1].z : add[1].w);
-    const float zf = zfv[r] + (r == 0 ? add[2].x : r == 1 ? add[2].y : r == 2 ? add[2].z : add[2].w);
-    const float zo = zov[r] + (r == 0 ? add[3].x : r == 1 ? add[3].y : r == 2 ? add[3].z : add[3].w);
-    const float gi = fast_sigmoid(zi), gj = fast_tanh(zj), gf = fast_sigmoid(zf + 1.0f), go = fast_sigmoid(zo);
-    cn[r] = co[r] * gf + gi * gj;
-    hn[r] = fast_tanh(cn[r]) * go;
-  }
-  float4 c4 = make_float4(cn[0], cn[1], cn[2], cn[3]);
-  float4 h4 = make_float4(hn[0], hn[1], hn[2], hn[3]);
-  float4 o4 = h4;
-  if (masked) { c4 = c_old; h4 = h_prev; o4 = make_float4(0.f, 0.f, 0.f, 0.f); }
-  *reinterpret_cast<float4*>(jb.c_out + sidx) = c4;
-  *reinterpret_cast<float4*>(jb.h_new + sidx) = h4;
-  // the planes the next step's MFMAs read: [3][L/8][R][8], units 4 t4 .. 4 t4 + 3 = half of a k8 group
-  const size_t plane_elems = (size_t)(L / 8) * R * 8;
-  const size_t poff = ((size_t)(t4 >> 1) * R + grc) * 8 + (size_t)(t4 & 1) * 4;
-  if (jb.h_new_b) store_planes(jb.h_new_b, plane_elems, poff, h4);
-  const size_t oidx = (size_t)orow * L + 4 * t4;
-  if (jb.out_seq) *reinterpret_cast<float4*>(jb.out_seq + oidx) = o4;
-  if (jb.h_drop) {                // dropped copy of the OUTPUT for the layer above
-    const float4 dm = *reinterpret_cast<const float4*>(jb.drop + oidx);
-    const float4 hd = make_float4(h4.x * dm.x, h4.y * dm.y, h4.z * dm.z, h4.w * dm.w);
-    *reinterpret_cast<float4*>(jb.h_drop + sidx) = hd;
-    if (jb.h_drop_b) store_planes(jb.h_drop_b, plane_elems, poff, hd);
-  }
-  if (jb.fin_c && jb.seq_len && jb.t == jb.seq_len[orow] - 1) {   // the row's last valid step
-    const size_t fidx = ((size_t)t4 * R + orow) * 4;
-    *reinterpret_cast<float4*>(jb.fin_c + fidx) = c4;
-    *reinterpret_cast<float4*>(jb.fin_h + fidx) = h4;
-    if (jb.fin_h_b)
-      store_planes(jb.fin_h_b, plane_elems, ((size_t)(t4 >> 1) * R + orow) * 8 + (size_t)(t4 & 1) * 4, h4);
-  }
+  for (int r = 0; r < 4; ++r) { z[0][r] = acc[0][r]; z[1][r] = acc[1][r]; }
+  lstm_add_last<4>(z, in);
+  lstm_cell_update<4, LSTM_OUT_PLANES>(jb, L, at, in, z);
 }
 
 // weights -> three bf16 planes in fragment order (see the header): one thread per 16-byte fragment
@@ -390,7 +294,7 @@ __global__ __launch_bounds__(256) void split_state_b3_kernel(const float* __rest
 }
 
 template <int NS, int RG, int VAR = 0>
-void launch_tile3(const LstmJobs3& js, int njobs, int N, int L, hipStream_t s) {
+void launch_tile3(const LstmJobs& js, int njobs, int N, int L, hipStream_t s) {
   static std::atomic<uint64_t> attr{0};
   const int lds = NS * T3<RG>::STAGE;
   ensure_dynamic_lds(reinterpret_cast<const void*>(&lstm_tile3_kernel<NS, RG, VAR>), lds, attr);
@@ -418,11 +322,7 @@ bool lstm_tile3_supported(const LstmJob* jobs, int njobs, int L) {
 }
 
 void launch_lstm_tile3(const LstmJob* jobs, int njobs, int N, int L, hipStream_t s, int variant) {
-  LstmJobs3 js;
-  for (int i = 0; i < 2; ++i) {
-    if (i < njobs) js.j[i] = jobs[i];
-    else { js.j[i] = LstmJob{}; js.j[i].active = 0; }
-  }
+  const LstmJobs js = lstm_jobs(jobs, njobs);
   // default: 128-row workgroups (16 waves, 4 stages of 36 KiB) when the launch has at least two
   // 128-row blocks per job; variants (n2nmn_debug_lstm_bench): 4xx = 64-row workgroups
   static const int dflt = N2NMN_KNOB_INT("N2NMN_TILE3_VARIANT", 0);

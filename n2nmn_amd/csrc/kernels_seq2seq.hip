@@ -5,8 +5,7 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "device_utils.h"
-#include "kernels.h"
+#include "lstm_cell.h"
 
 namespace n2nmn {
 
@@ -36,10 +35,6 @@ namespace {
 // ---------------------------------------------------------------------------------------------
 constexpr int LSTM_WAVES = 8;
 constexpr int LSTM_THREADS = LSTM_WAVES * 64;
-
-struct LstmJobs {
-  LstmJob j[2];
-};
 
 // DBG: 0 normal, 1 = pin all loads before the MFMAs (sched_barrier), 2 = loads only (no MFMA),
 // 3 = MFMA only (no loads), 4 = neither, 6 = weight loads only, 7 = state loads only
@@ -146,42 +141,19 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_step_kernel(LstmJobs jobs, 
   const int erow = tid >> 2, ul = tid & 3;
   const int gr = row0 + erow;
   const bool eact = tid < 4 * ROWS && gr < N;
-  const int orow = (eact && jb.perm) ? jb.perm[gr] : gr;   // original row of state row gr
+  const LstmCellAt at{gr, eact ? lstm_orow(jb, gr) : gr, tile, ul};
   if (row0 >= nact && jb.mode == 0 && !jb.save_gates) {
-    // Every row of this tile is past its length (length-sorted encoder).  Such rows are never read
-    // again: the recurrence only contracts over rows of tiles that are still active, c is updated
-    // in place, and a row's final state was captured at its last valid step (fin_c / fin_h).  All
-    // that is left of dynamic_rnn's semantics (Appendix A.2) is the zero output row.
-    if (eact && jb.out_seq) jb.out_seq[(size_t)orow * L + 4 * tile + ul] = 0.f;
+    // every row of this tile is past its length (length-sorted encoder)
+    if (eact) lstm_zero_output<1>(jb, L, at.orow, at);
     return;
   }
-  float add[4] = {0.f, 0.f, 0.f, 0.f};
-  float c_old = 0.f, h_prev = 0.f;
-  bool masked = false;
+  LstmCellIn<1> in;
   if (eact) {
     if (jb.mode == 1) {
 #pragma unroll
-      for (int g = 0; g < 4; ++g) add[g] = jb.bias ? jb.bias[16 * tile + g * 4 + ul] : 0.f;
+      for (int g = 0; g < 4; ++g) in.add[g][0] = jb.bias ? jb.bias[16 * tile + g * 4 + ul] : 0.f;
     } else {
-      const int u = 4 * tile + ul;
-      if (jb.xtab) {
-        const int xi = jb.xidx ? jb.xidx[orow] : jb.xidx_const;
-        const float* xr = jb.xtab + (size_t)xi * 4 * L + 16 * tile + ul;   // tile column order
-#pragma unroll
-        for (int g = 0; g < 4; ++g) add[g] = xr[4 * g];
-      } else {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) add[g] = jb.bias[16 * tile + 4 * g + ul];   // tile order
-      }
-      const size_t idx = (size_t)gr * L + u;
-      // the cell state shares the k-interleaved layout of h: a tile's 64 rows x 4 units are one
-      // contiguous KB instead of 64 sixteen-byte pieces of 64 different lines
-      const size_t sidx = jb.hp_R > 0 ? ((size_t)tile * jb.hp_R + gr) * 4 + ul : idx;
-      c_old = jb.c_in[sidx];
-      if (jb.seq_len && jb.t >= jb.seq_len[orow]) { // dynamic_rnn past the length (A.2)
-        masked = true;
-        h_prev = jb.h_old[sidx];
-      }
+      lstm_cell_prefetch<1>(jb, L, at, in);
     }
   }
 
@@ -223,51 +195,21 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_step_kernel(LstmJobs jobs, 
   __syncthreads();
 
   if (eact) {
-    float z[4];
+    float z[4][1];
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      float s = add[g];
+      float s = in.add[g][0];
 #pragma unroll
       for (int ww = 0; ww < LSTM_WAVES; ++ww) s += part[ww][erow][g * 4 + ul];
-      z[g] = s;
+      z[g][0] = s;
     }
     if (jb.mode == 1) {                           // plain linear: out = z + bias
 #pragma unroll
       for (int g = 0; g < 4; ++g)
-        jb.h_new[(size_t)gr * jb.ldo + 16 * tile + g * 4 + ul] = z[g];
+        jb.h_new[(size_t)gr * jb.ldo + 16 * tile + g * 4 + ul] = z[g][0];
       return;
     }
-    const size_t idx = (size_t)gr * L + 4 * tile + ul;
-    const float gi = fast_sigmoid(z[0]), gj = fast_tanh(z[1]), gf = fast_sigmoid(z[2] + 1.0f),
-                go = fast_sigmoid(z[3]);
-    float c_new = c_old * gf + gi * gj;
-    float h_new = fast_tanh(c_new) * go;
-    float o = h_new;
-    if (masked) { c_new = c_old; h_new = h_prev; o = 0.f; }
-    const size_t sidx = jb.hp_R > 0 ? ((size_t)tile * jb.hp_R + gr) * 4 + ul : idx;
-    jb.c_out[sidx] = c_new;
-    jb.h_new[sidx] = h_new;
-    // split-operand bf16 mode: the tail steps of a pass run here (exact fp32) but later steps / the decoder
-    // read the bf16 planes of what they write
-    if (jb.h_new_b && jb.hp_R > 0) store_plane1(jb.h_new_b, L, jb.hp_R, 4 * tile + ul, gr, h_new);
-    const size_t oidx = (size_t)orow * L + 4 * tile + ul;
-    if (jb.save_gates) {          // training: keep what the cell backward needs (masked rows keep
-      jb.save_gates[oidx] = make_float4(gi, gj, gf, go);   // finite values; their dz is zero)
-      jb.save_c[oidx] = c_new;
-      jb.save_h[oidx] = h_new;
-    }
-    if (jb.out_seq) jb.out_seq[oidx] = o;
-    if (jb.h_drop) {              // dropped copy of the OUTPUT for the layer above
-      const float hd = h_new * jb.drop[oidx];
-      jb.h_drop[jb.hp_R > 0 ? ((size_t)tile * jb.hp_R + gr) * 4 + ul : idx] = hd;
-      if (jb.h_drop_b && jb.hp_R > 0) store_plane1(jb.h_drop_b, L, jb.hp_R, 4 * tile + ul, gr, hd);
-      if (jb.save_hd) jb.save_hd[oidx] = hd;
-    }
-    if (jb.fin_c && jb.seq_len && jb.t == jb.seq_len[orow] - 1) {   // the row's last valid step
-      jb.fin_c[((size_t)tile * jb.hp_R + orow) * 4 + ul] = c_new;
-      jb.fin_h[((size_t)tile * jb.hp_R + orow) * 4 + ul] = h_new;
-      if (jb.fin_h_b) store_plane1(jb.fin_h_b, L, jb.hp_R, 4 * tile + ul, orow, h_new);
-    }
+    lstm_cell_update<1, LSTM_OUT_SAVE | LSTM_OUT_PLANES>(jb, L, at, in, z);
   }
 }
 
@@ -345,33 +287,13 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_step_wide_kernel(LstmJobs j
   const int tile = 2 * pair + tloc;
   const int gr = row0 + erow;
   const bool eact = tid < 8 * ROWS && gr < N;
-  const int orow = (eact && jb.perm) ? jb.perm[gr] : gr;
+  const LstmCellAt at{gr, eact ? lstm_orow(jb, gr) : gr, tile, ul};
   if (row0 >= nact && !jb.save_gates) {        // see lstm_step_kernel: only the zero output row is left
-    if (eact && jb.out_seq) jb.out_seq[(size_t)orow * L + 4 * tile + ul] = 0.f;
+    if (eact) lstm_zero_output<1>(jb, L, at.orow, at);
     return;
   }
-  float add[4] = {0.f, 0.f, 0.f, 0.f};
-  float c_old = 0.f, h_prev = 0.f;
-  bool masked = false;
-  if (eact) {
-    const int u = 4 * tile + ul;
-    if (jb.xtab) {
-      const int xi = jb.xidx ? jb.xidx[orow] : jb.xidx_const;
-      const float* xr = jb.xtab + (size_t)xi * 4 * L + 16 * tile + ul;     // tile column order
-#pragma unroll
-      for (int g = 0; g < 4; ++g) add[g] = xr[4 * g];
-    } else {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) add[g] = jb.bias[16 * tile + 4 * g + ul];     // tile order
-    }
-    const size_t idx = (size_t)gr * L + u;
-    const size_t sidx = jb.hp_R > 0 ? ((size_t)tile * jb.hp_R + gr) * 4 + ul : idx;
-    c_old = jb.c_in[sidx];
-    if (jb.seq_len && jb.t >= jb.seq_len[orow]) {
-      masked = true;
-      h_prev = jb.h_old[sidx];
-    }
-  }
+  LstmCellIn<1> in;
+  if (eact) lstm_cell_prefetch<1>(jb, L, at, in);
 
   f32x4 acc[MT][2];
 #pragma unroll
@@ -401,45 +323,15 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_step_wide_kernel(LstmJobs j
   __syncthreads();
 
   if (eact) {
-    float z[4];
+    float z[4][1];
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      float s = add[g];
+      float s = in.add[g][0];
 #pragma unroll
       for (int ww = 0; ww < LSTM_WAVES; ++ww) s += part[ww][erow][16 * tloc + g * 4 + ul];
-      z[g] = s;
+      z[g][0] = s;
     }
-    const size_t idx = (size_t)gr * L + 4 * tile + ul;
-    const float gi = fast_sigmoid(z[0]), gj = fast_tanh(z[1]), gf = fast_sigmoid(z[2] + 1.0f),
-                go = fast_sigmoid(z[3]);
-    float c_new = c_old * gf + gi * gj;
-    float h_new = fast_tanh(c_new) * go;
-    float o = h_new;
-    if (masked) { c_new = c_old; h_new = h_prev; o = 0.f; }
-    const size_t sidx = jb.hp_R > 0 ? ((size_t)tile * jb.hp_R + gr) * 4 + ul : idx;
-    jb.c_out[sidx] = c_new;
-    jb.h_new[sidx] = h_new;
-    // split-operand bf16 mode: the tail steps of a pass run here (exact fp32) but later steps / the decoder
-    // read the bf16 planes of what they write
-    if (jb.h_new_b && jb.hp_R > 0) store_plane1(jb.h_new_b, L, jb.hp_R, 4 * tile + ul, gr, h_new);
-    const size_t oidx = (size_t)orow * L + 4 * tile + ul;
-    if (jb.save_gates) {
-      jb.save_gates[oidx] = make_float4(gi, gj, gf, go);
-      jb.save_c[oidx] = c_new;
-      jb.save_h[oidx] = h_new;
-    }
-    if (jb.out_seq) jb.out_seq[oidx] = o;
-    if (jb.h_drop) {              // dropped copy of the OUTPUT for the layer above
-      const float hd = h_new * jb.drop[oidx];
-      jb.h_drop[jb.hp_R > 0 ? ((size_t)tile * jb.hp_R + gr) * 4 + ul : idx] = hd;
-      if (jb.h_drop_b && jb.hp_R > 0) store_plane1(jb.h_drop_b, L, jb.hp_R, 4 * tile + ul, gr, hd);
-      if (jb.save_hd) jb.save_hd[oidx] = hd;
-    }
-    if (jb.fin_c && jb.seq_len && jb.t == jb.seq_len[orow] - 1) {
-      jb.fin_c[((size_t)tile * jb.hp_R + orow) * 4 + ul] = c_new;
-      jb.fin_h[((size_t)tile * jb.hp_R + orow) * 4 + ul] = h_new;
-      if (jb.fin_h_b) store_plane1(jb.fin_h_b, L, jb.hp_R, 4 * tile + ul, orow, h_new);
-    }
+    lstm_cell_update<1, LSTM_OUT_SAVE | LSTM_OUT_PLANES>(jb, L, at, in, z);
   }
 }
 
@@ -1619,11 +1511,7 @@ __global__ __launch_bounds__(256) void word_vecs_kernel(const float* __restrict_
 
 void launch_lstm_step(const LstmJob* jobs, int njobs, int N, int L, int rows_per_wg,
                       hipStream_t s, int wide) {
-  LstmJobs js;
-  for (int i = 0; i < 2; ++i) {
-    if (i < njobs) js.j[i] = jobs[i];
-    else { js.j[i] = LstmJob{}; js.j[i].active = 0; }
-  }
+  const LstmJobs js = lstm_jobs(jobs, njobs);
   int nt = 0;
   bool cells = true;
   for (int i = 0; i < njobs; ++i) {
@@ -1676,11 +1564,7 @@ __global__ void unpack_h2_kernel(const float* __restrict__ a, const float* __res
 // debug: the same launch with a kernel variant (see lstm_mma DBG); variant 5 = empty kernel
 void launch_lstm_step_dbg(const LstmJob* jobs, int njobs, int N, int L, int rows_per_wg,
                           int variant, hipStream_t s) {
-  LstmJobs js;
-  for (int i = 0; i < 2; ++i) {
-    if (i < njobs) js.j[i] = jobs[i];
-    else { js.j[i] = LstmJob{}; js.j[i].active = 0; }
-  }
+  const LstmJobs js = lstm_jobs(jobs, njobs);
   int nt = 0;
   for (int i = 0; i < njobs; ++i) nt = jobs[i].ntiles > nt ? jobs[i].ntiles : nt;
   dim3 g4(nt, njobs, (N + 63) / 64), g2(nt, njobs, (N + 31) / 32), b(LSTM_THREADS);

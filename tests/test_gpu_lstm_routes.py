@@ -4,19 +4,20 @@ exposes (encoder outputs / h_transformed / final states, the teacher-forced deco
 
 Which kernel runs a pipelined two-layer encoder launch (csrc/capi.cpp encoder_impl; launch k runs
 layer-0 step k and layer-1 step k - 1):
-  * lstm_wide (capi.cpp:326): 'throughput' and 'throughput_bf16x3' ask for the tile kernels (2),
+  * lstm_wide (capi.cpp): 'throughput' and 'throughput_bf16x3' ask for the tile kernels (2),
     'throughput_ksplit' for the K-split tiles (1), 'latency' for neither (0);
-  * capi.cpp:516: with a host copy of the lengths (Engine.seq2seq passes one whenever seq_len is a
+  * encoder_impl: with a host copy of the lengths (Engine.seq2seq passes one whenever seq_len is a
     numpy array) a launch whose active-row count act[min(k, T - 1)] is <= tile_min_rows (default 192,
-    capi.cpp:345) takes the K-split tiles -- tile_min_rows 0 keeps the tile kernel at every step with
-    an active row, 1 << 30 never uses it; lengths handed over as a device tensor only leave the tile
+    capi.cpp tile_min_rows) takes the K-split tiles -- tile_min_rows 0 keeps the tile kernel at every step
+    with an active row, 1 << 30 never uses it; lengths handed over as a device tensor only leave the tile
     kernel at every step;
-  * launch_lstm_step (csrc/kernels_seq2seq.hip:1601): wide >= 2 and N >= 128 -> lstm_tile_kernel<4, 0>
+  * launch_lstm_step (csrc/kernels_seq2seq.hip): wide >= 2 and N >= 128 -> lstm_tile_kernel<4, 0>
     (kernels_lstm_tile.hip: row blocks past n_active are skipped, the ids behind them write the zero
     output rows); wide == 1 -> lstm_step_wide_kernel<2> (32-row tiles); wide == 0 -> lstm_step_kernel<4, 0>;
-  * bf16x3 (capi.cpp:518-525): lstm_tile3 while wide == 2, the exact K-split tiles (which write the
+  * bf16x3 (capi.cpp lstm_step_route): lstm_tile3 while wide == 2, the exact K-split tiles (which write the
     bf16 planes of what they produce) once the count drops to tile_min_rows.
-The teacher-forced decoder (no eos_retire) takes lstm_wide's choice at every step (capi.cpp:718-727).
+The teacher-forced decoder (no eos_retire) takes lstm_wide's choice at every step (capi.cpp decoder_impl,
+through lstm_step_route).
 
 Oracle: oracle/n2nmn_oracle.py encoder_forward / decoder_forward in float64.  Every question of the
 oracle is independent of the others, so it runs ONCE per length profile over a pool of questions; the
@@ -118,11 +119,16 @@ def _take_dec(dec, cols):
                 neg_entropy=dec['neg_entropy'][cols])
 
 
+def _cols(n):
+    cols = np.random.default_rng(1000 + n).permutation(n)
+    assert (cols != np.arange(n)).any()
+    return cols
+
+
 def _case(profile, n):
     """the N-row batch of a profile: pool columns 0 .. n - 1 in a shuffled order, with its oracle"""
     batch, gt, enc, dec = _pool(profile)
-    cols = np.random.default_rng(1000 + n).permutation(n)
-    assert (cols != np.arange(n)).any()
+    cols = _cols(n)
     b = dict(input_seq_batch=np.ascontiguousarray(batch['input_seq_batch'][:, cols]),
              seq_length_batch=np.ascontiguousarray(batch['seq_length_batch'][cols]))
     return b, np.ascontiguousarray(gt[:, cols]), _take_enc(enc, cols), _take_dec(dec, cols)
@@ -198,6 +204,41 @@ def test_route_matches_the_oracle(eng, route, profile, n):
     assert np.array_equal(out['predicted_tokens'], gt)
     diffs = _check_all(out, batch, enc, dec)
     print('\nROUTE %-17s %s%-4d %s' % (route, profile, n, ' '.join('%s=%.2e' % kv for kv in diffs.items())))
+
+
+def _dropout_pool():
+    """profile (a)'s pool with DropoutWrapper on the output of layer 0 of both LSTMs: the {0, 1} keep masks
+    (keep probability 0.5) and the oracle under them, computed once"""
+    if 'dropout' not in _pools:
+        batch, gt, _, _ = _pool('a')
+        rng = np.random.default_rng(77)
+        m_enc = rng.integers(0, 2, size=(T, POOL, D.lstm_dim)).astype(np.float32)
+        m_dec = rng.integers(0, 2, size=(D.T_decoder, POOL, D.lstm_dim)).astype(np.float32)
+        enc = O.encoder_forward(W, batch['input_seq_batch'], batch['seq_length_batch'], np.float64, drop0=m_enc)
+        P, Wv, bv = O.build_validity_mats(NAMES)
+        dec = O.decoder_forward(W, enc, P, Wv, bv, D.T_decoder, np.float64, use_gt_layout=True, gt_layout=gt,
+                                drop0=m_dec)
+        _pools['dropout'] = (m_enc, m_dec, enc, dec)
+    return _pools['dropout']
+
+
+@pytest.mark.parametrize('n', [129, 257])
+@pytest.mark.parametrize('route', list(ROUTES))
+def test_route_with_dropout_matches_the_oracle(eng, route, n):
+    """The dropped copy of layer 0's output (LstmJob::h_drop: what layer 1 reads; the recurrent state stays
+    h) is the one branch of the cell update that no inference test reaches per route.  Profile (a) at
+    129 rows (the 64-row block edge plus one) and 257 (lstm_tile3's 128-row workgroups, from 256 rows on),
+    multipliers 2 * mask in float32 for the encoder and the teacher-forced decoder: h_drop on all four step
+    kernels, and its bf16 planes (h_drop_b) on lstm_tile3 and on the K-split tail of the bf16x3 route.  No
+    route rejects dropout.  Bars: those of test_route_matches_the_oracle."""
+    batch, gt, _, _ = _case('a', n)
+    m_enc, m_dec, enc, dec = _dropout_pool()
+    cols = _cols(n)
+    drops = tuple(np.ascontiguousarray(2 * m[:, cols]) for m in (m_enc, m_dec))
+    out = _run(eng, route, batch, gt, debug=True, dropout=drops)
+    assert np.array_equal(out['predicted_tokens'], gt)
+    diffs = _check_all(out, batch, _take_enc(enc, cols), _take_dec(dec, cols))
+    print('\nDROPOUT %-17s a%-4d %s' % (route, n, ' '.join('%s=%.2e' % kv for kv in diffs.items())))
 
 
 PER_ROW = {'encoder_outputs': 1, 'encoder_h_transformed': 1, 'encoder_states': 2, 'token_scores': 1,
