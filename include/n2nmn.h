@@ -745,6 +745,56 @@ int n2nmn_fc_forward(n2nmn_ctx *ctx, const float *A, const float *W, const float
  * ---------------------------------------------------------------------------------------- */
 uint32_t n2nmn_crc32c(uint32_t crc, const void *data, size_t n);
 
+/* ------------------------------------------------------------------------------------------
+ * (9) VGG-16 pool5 feature extractor: image -> the image_feat grid of the CLEVR entry points.
+ *     Replaces: models_clevr/vgg_net.py:16-56 (vgg_pool5: 13 SAME 3x3 conv + bias + ReLU, five 2x2
+ *     stride-2 SAME max-pools) as driven by exp_clevr/data/extract_visual_features_vgg_pool5.py:23-38
+ *     (tf.train.Saver.restore of vgg_net.tfmodel, `im - channel_mean`, pool5.eval).  Exact fp32
+ *     (v_mfma_f32_32x32x2_f32); csrc/kernels_vgg.hip, DESIGN.md section 15.
+ *     A model of its own, hence a handle of its own: n2nmn_vgg holds the 26 variables, their packed
+ *     form and every activation buffer.  Everything is allocated in n2nmn_vgg_create and freed in
+ *     n2nmn_vgg_destroy.  One handle serves one thread and one stream at a time.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct n2nmn_vgg n2nmn_vgg;
+/* Buffers for up to max_N images of up to max_H x max_W pixels (about 190 MB per 320 x 480 image: every
+ * layer keeps its activation, n2nmn_vgg_get_layer).  N2NMN_ECAPACITY if the largest activation,
+ * max_N (max_H + 2) (max_W + 2) 64 floats, reaches 4 GiB. */
+int n2nmn_vgg_create(int device, int max_N, int max_H, int max_W, n2nmn_vgg **out);
+int n2nmn_vgg_destroy(n2nmn_vgg *vgg);
+/* One variable by the reference's name inside its scope: "conv1_1/weights" [3,3,3,64], "conv1_1/biases"
+ * [64], ... "conv5_3/weights" [3,3,512,512], "conv5_3/biases" [512] (util/cnn.py:19-25: HWIO weights).
+ * `data`: device pointer to contiguous fp32, copied before the call returns.  Unknown name: N2NMN_EKEY;
+ * wrong shape: N2NMN_EINVAL; both with the expected names / shape in n2nmn_last_error(). */
+int n2nmn_vgg_set_weight(n2nmn_vgg *vgg, const char *name, const float *data, const int64_t *shape,
+                         int ndim);
+/* Pack the weights into the MFMA operand layout (PK pack), once.  Needed after the
+ * variables change and before a forward; N2NMN_ENOWEIGHT names the first variable never set.
+ * Asynchronous on `stream`. */
+int n2nmn_vgg_commit(n2nmn_vgg *vgg, n2nmn_stream stream);
+/* out [N, ceil(H/32), ceil(W/32), 512] = vgg_pool5(images - channel_mean), channel_mean = (123.68, 116.779,
+ * 103.939) (vgg_net.py:14).  images: DEVICE [N,H,W,3] RGB, raw pixel values (the mean is subtracted here),
+ * uint8 if is_uint8 != 0, else fp32.  N <= max_N, H <= max_H, W <= max_W (N2NMN_ECAPACITY).  Asynchronous
+ * on `stream`: no host synchronisation, no allocation.  (A call whose H x W differs from the previous
+ * call's first clears the activation buffers, on `stream`.) */
+int n2nmn_vgg_forward(n2nmn_vgg *vgg, const void *images, int is_uint8, int N, int H, int W, float *out,
+                      n2nmn_stream stream);
+/* The activation of one layer ("conv1_1" ... "conv5_3", "pool1" ... "pool5"; after its ReLU) of the LAST
+ * forward, as a dense [N,h,w,C] copy into `out` (device, `capacity` floats); shape receives N, h, w, C.
+ * out == NULL: only the shape.  Asynchronous on `stream`.  For tests and for finding where an error starts. */
+int n2nmn_vgg_get_layer(n2nmn_vgg *vgg, const char *layer, float *out, int64_t capacity, int64_t shape[4],
+                        n2nmn_stream stream);
+/* Re-launch one layer ("conv1_2" ... "pool5") of the LAST forward `iters` times inside one HIP event pair
+ * (3 warm-up launches before it) and return the mean microseconds per launch.  Synchronises. */
+int n2nmn_vgg_debug_replay(n2nmn_vgg *vgg, const char *layer, int iters, double *us_avg,
+                           n2nmn_stream stream);
+/* Single layers on dense device tensors, through the kernels a forward uses (tests of the tile's edges):
+ * out [N,H,W,Cout] = relu(conv3x3_SAME(in [N,H,W,Cin], w [3,3,Cin,Cout]) + bias), Cin % 32 == 0,
+ * Cout % 4 == 0; out [N,ceil(H/2),ceil(W/2),C] = max_pool_2x2_SAME(in [N,H,W,C]), C % 4 == 0.
+ * Both allocate temporaries and synchronise `stream`. */
+int n2nmn_vgg_debug_conv(const float *in, const float *w, const float *bias, float *out, int N, int H,
+                         int W, int Cin, int Cout, n2nmn_stream stream);
+int n2nmn_vgg_debug_pool(const float *in, float *out, int N, int H, int W, int C, n2nmn_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

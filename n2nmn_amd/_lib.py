@@ -159,6 +159,16 @@ SYMBOLS = [
     ('n2nmn_crc32c', C.c_uint32, [C.c_uint32, C.c_char_p, C.c_size_t]),
     ('n2nmn_debug_set', _I, [_P, C.c_char_p, C.c_char_p]),
     ('n2nmn_automaton_forces_eos', _I, [_P, _P, _P, _P, _I, _I]),
+    # section 9: the VGG-16 pool5 feature extractor (a handle of its own)
+    ('n2nmn_vgg_create', _I, [_I, _I, _I, _I, C.POINTER(_P)]),
+    ('n2nmn_vgg_destroy', _I, [_P]),
+    ('n2nmn_vgg_set_weight', _I, [_P, C.c_char_p, _P, C.POINTER(C.c_int64), _I]),
+    ('n2nmn_vgg_commit', _I, [_P, _P]),
+    ('n2nmn_vgg_forward', _I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    ('n2nmn_vgg_get_layer', _I, [_P, C.c_char_p, _P, C.c_int64, C.POINTER(C.c_int64), _P]),
+    ('n2nmn_vgg_debug_replay', _I, [_P, C.c_char_p, _I, C.POINTER(C.c_double), _P]),
+    ('n2nmn_vgg_debug_conv', _I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    ('n2nmn_vgg_debug_pool', _I, [_P, _P, _I, _I, _I, _I, _P]),
 ]
 
 

@@ -26,18 +26,14 @@
 #include <algorithm>
 
 #include "device_utils.h"
+#include "gemm_dma_tile.h"
 #include "kernels.h"
 
 namespace n2nmn {
 
 namespace {
 
-constexpr int DM = 128, DN = 128, DK = 32;
-constexpr int DMA_THREADS = 512;
-constexpr int DSTAGE = (DM * DK + DK * DN) * 4;          // 32 KiB: A image 16 KiB, then B image
-constexpr int DB_IMAGE = DM * DK * 4;
-
-struct Frag { float4 a; float4 b[2]; };
+using namespace dma_tile;       // the tile itself: gemm_dma_tile.h (shared with kernels_vgg.hip)
 
 __device__ __forceinline__ void gemm_dma_body(const GemmArgs& a, const int bx, const int by) {
   extern __shared__ __attribute__((aligned(1024))) char smem[];
@@ -61,7 +57,6 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& a, const int bx, c
     __syncthreads();
     if (!need) return;
   }
-  const uint32_t lds0 = (uint32_t)(uintptr_t)smem;
   const int nst = a.Kp / DK;
 
   // ---- DMA roles: wave w moves A rows [16w, 16w + 16) (two pieces of 8 rows x 128 B) and the k4
@@ -69,7 +64,7 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& a, const int bx, c
   uint32_t a_off[2], a_sw[2];
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
-    const int row = 16 * w + 8 * u + (lane >> 3);
+    const int row = a_row(w, u, lane);
     int gm = m0 + row;
     gm = gm < M ? gm : M - 1;
     if (a.group_idx) {
@@ -77,77 +72,22 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& a, const int bx, c
       gm = a.group_idx[g] * a.group_size + (gm - g * a.group_size);
     }
     a_off[u] = (uint32_t)gm * (uint32_t)a.lda * 4u;
-    a_sw[u] = (uint32_t)((lane & 7) ^ ((row >> 1) & 7));      // chunk this lane fetches
+    a_sw[u] = a_chunk(row, lane);                             // chunk this lane fetches
   }
   const float* const Ap = a.A;
-  const float* const Bp = a.Bp;
   const uint32_t b_off = ((uint32_t)w * (uint32_t)a.Np + (uint32_t)n0 + (uint32_t)lane) * 16u;
   const uint32_t b_slab = 8u * (uint32_t)a.Np * 16u;            // bytes per stage of B (8 k4 slabs)
   const int Klast = a.K - 4;
-  auto issue = [&](int s) {
-    const uint32_t st = lds0 + (uint32_t)(s & 1) * DSTAGE;
+  f32x16 acc[2];
+  accumulate(smem, nst, a.Bp, b_off, b_slab, [&](int s, uint32_t st) {
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       // columns past K (Kp padding) meet zero weights: any finite in-bounds value will do
       const int k = min(s * DK + 4 * (int)a_sw[u], Klast);
-      glds16(Ap, a_off[u] + (uint32_t)k * 4u, st + (uint32_t)(16 * w + 8 * u) * 128u);
+      glds16(Ap, a_off[u] + (uint32_t)k * 4u, st + a_piece_lds(w, u));
     }
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-      glds16(Bp, b_off + (uint32_t)s * b_slab + (uint32_t)u * 1024u,
-             st + DB_IMAGE + (uint32_t)(w * DN + 64 * u) * 16u);
-  };
-
-  // ---- fragment addressing -------------------------------------------------------------------------
+  }, acc);
   const int li = lane & 31, kh = lane >> 5;
-  const int arow = wm * 32 + li;
-  const uint32_t a_base = (uint32_t)arow * 128u;
-  const uint32_t a_x = (uint32_t)((arow >> 1) & 7);
-  const uint32_t b_base = (uint32_t)DB_IMAGE + (uint32_t)(wn * 64 + li) * 16u;
-  auto read_frag = [&](int s, int g) {
-    const char* st = smem + (size_t)(s & 1) * DSTAGE;
-    const uint32_t chunk = (uint32_t)(2 * g + kh);
-    Frag f;
-    f.a = *reinterpret_cast<const float4*>(st + a_base + ((chunk ^ a_x) << 4));
-    f.b[0] = *reinterpret_cast<const float4*>(st + b_base + chunk * (DN * 16u));
-    f.b[1] = *reinterpret_cast<const float4*>(st + b_base + chunk * (DN * 16u) + 32u * 16u);
-    return f;
-  };
-  f32x16 acc[2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-  auto mma = [&](const Frag& f) {
-#pragma unroll
-    for (int t = 0; t < 2; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.a.x, f.b[t].x, acc[t], 0, 0, 0);
-#pragma unroll
-    for (int t = 0; t < 2; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.a.y, f.b[t].y, acc[t], 0, 0, 0);
-#pragma unroll
-    for (int t = 0; t < 2; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.a.z, f.b[t].z, acc[t], 0, 0, 0);
-#pragma unroll
-    for (int t = 0; t < 2; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.a.w, f.b[t].w, acc[t], 0, 0, 0);
-  };
-
-  issue(0);
-  for (int s = 0; s < nst; ++s) {
-    // this wave's pieces of stage s have landed; after the barrier everyone's have, and everyone is
-    // done reading stage s - 1, whose buffer the DMA of stage s + 1 refills under this stage's MFMAs
-    wait_vm<0>();
-    __builtin_amdgcn_s_barrier();
-    if (s + 1 < nst) issue(s + 1);
-    Frag P = read_frag(s, 0);
-    Frag Q = read_frag(s, 1);
-    __builtin_amdgcn_sched_barrier(0);       // (left alone, hipcc sinks the reads below the MFMAs)
-    mma(P);
-    P = read_frag(s, 2);
-    __builtin_amdgcn_sched_barrier(0);
-    mma(Q);
-    Q = read_frag(s, 3);
-    __builtin_amdgcn_sched_barrier(0);
-    mma(P);
-    mma(Q);
-  }
 
   // ---- epilogue: C/D layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
 #pragma unroll
