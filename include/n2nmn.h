@@ -795,6 +795,73 @@ int n2nmn_vgg_debug_conv(const float *in, const float *w, const float *bias, flo
                          int W, int Cin, int Cout, n2nmn_stream stream);
 int n2nmn_vgg_debug_pool(const float *in, float *out, int N, int H, int W, int C, n2nmn_stream stream);
 
+/* ------------------------------------------------------------------------------------------
+ * (10) ResNet-152 res5c feature extractor: image -> the (14, 14, 2048) image_feat grid of the VQA entry
+ *     points (the reference's exp_vqa README: "the res5c layer of the ResNet-152 network ... HxWxC", which it
+ *     leaves to an outside Caffe installation).  The network is He et al.'s as deployed in Caffe, from the
+ *     published description -- the reference holds no ResNet code: conv1 7x7/2 + pool1 3x3/2 (ceil mode) +
+ *     bottleneck stages res2 .. res5 with the stride on branch2a and branch1.  Exact fp32; batch-norm and
+ *     scale are folded into the convolutions BEFORE they get here (n2nmn_amd/resnet.py fold_batchnorm), so
+ *     a layer is convolution + bias (+ residual) (+ ReLU).  csrc/kernels_resnet.hip and, for every 3x3,
+ *     the unchanged kernel of section 9; DESIGN.md section 16.
+ *     A handle of its own, as section 9.  Everything is allocated in n2nmn_resnet_create and freed in
+ *     n2nmn_resnet_destroy.  One handle serves one thread and one stream at a time.
+ *     Layer names are Caffe's: "conv1", "pool1", then per block "<block>_branch1" (first block of a stage
+ *     only), "<block>_branch2a", "_branch2b", "_branch2c", <block> = res2a res2b res2c res3a res3b1 ..
+ *     res3b7 res4a res4b1 .. res4b35 res5a res5b res5c (a stage of up to 3 blocks is lettered a b c, a longer
+ *     one a b1 b2 ...).  The output of "<block>_branch2c" is formed by that convolution's epilogue and is the
+ *     BLOCK output relu(branch2c + shortcut), Caffe's blob "<block>"; "<block>" is accepted for it too.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct n2nmn_resnet n2nmn_resnet;
+/* Buffers for up to max_N images of up to max_H x max_W pixels: five haloed activation buffers (two the
+ * block outputs alternate between, branch2a's, branch2b's, the projection's; 448 x 448: 46 MB per image)
+ * and a copy of the input.  blocks: blocks per stage, (3, 8, 36, 3) for ResNet-152; base_width: 64 (stage
+ * widths base_width (1, 2, 4, 8), outputs 4 x that); N2NMN_EINVAL unless it is a multiple of 32.
+ * N2NMN_ECAPACITY if an activation reaches 4 GiB. */
+int n2nmn_resnet_create(int device, int max_N, int max_H, int max_W, const int blocks[4], int base_width,
+                        n2nmn_resnet **out);
+int n2nmn_resnet_destroy(n2nmn_resnet *resnet);
+/* The per-channel mean conv1 subtracts from the raw image (host pointer; default 123.68, 116.779, 103.939). */
+int n2nmn_resnet_set_mean(n2nmn_resnet *resnet, const float mean[3]);
+/* One FOLDED variable: "<layer>/weights" [k,k,Cin,Cout] (HWIO; k = 7 for conv1, 3 for branch2b, else 1),
+ * "<layer>/biases" [Cout].  `data`: device pointer to contiguous fp32, copied before the call returns.
+ * Unknown name: N2NMN_EKEY; wrong shape: N2NMN_EINVAL; both with what was expected in n2nmn_last_error(). */
+int n2nmn_resnet_set_weight(n2nmn_resnet *resnet, const char *name, const float *data, const int64_t *shape,
+                            int ndim);
+/* Pack the weights into the MFMA operand layout, once; N2NMN_ENOWEIGHT names the first variable never
+ * set.  Asynchronous on `stream`. */
+int n2nmn_resnet_commit(n2nmn_resnet *resnet, n2nmn_stream stream);
+/* out [N, h, w, 32 base_width] = the last block's output; h = H / 32 rounded up stage by stage
+ * (448 -> 14).  images: DEVICE [N,H,W,3], raw pixel values, uint8 if is_uint8 != 0, else fp32.
+ * N <= max_N, H <= max_H, W <= max_W (N2NMN_ECAPACITY); before a commit: N2NMN_ENOWEIGHT.  Asynchronous on
+ * `stream`: no host synchronisation, no allocation. */
+int n2nmn_resnet_forward(n2nmn_resnet *resnet, const void *images, int is_uint8, int N, int H, int W,
+                         float *out, n2nmn_stream stream);
+/* The output of one named layer for the LAST forward's images, as a dense [N,h,w,C] copy into `out` (device,
+ * `capacity` floats); shape receives N, h, w, C.  out == NULL: only the shape.  The activation buffers are
+ * shared between layers, so this runs the saved input up to `layer` again (bitwise the forward's values).
+ * Asynchronous on `stream`.  For tests and for finding where an error starts. */
+int n2nmn_resnet_get_layer(n2nmn_resnet *resnet, const char *layer, float *out, int64_t capacity,
+                           int64_t shape[4], n2nmn_stream stream);
+/* Re-launch one layer of the LAST forward -- or, with layer NULL or "", the whole network -- `iters` times
+ * inside one HIP event pair (3 warm-up rounds before it) and return the mean microseconds per round.  A
+ * single layer runs on whatever its input buffer holds by then (timing only); the first branch2a of a stage
+ * includes the clearing of its output buffer.  Synchronises. */
+int n2nmn_resnet_debug_replay(n2nmn_resnet *resnet, const char *layer, int iters, double *us_avg,
+                              n2nmn_stream stream);
+/* Single operations on dense device tensors, through the kernels a forward uses:
+ * stem: out [N,(H-1)/2+1,(W-1)/2+1,Cout] = relu(conv7x7_s2_p3(images - mean, w [7,7,3,Cout]) + bias), Cout % 4 == 0;
+ * pool: out [N,ho,wo,C] = max_pool_3x3_s2_ceil(in [N,H,W,C]), ho = ceil((H - 3) / 2) + 1, C % 4 == 0;
+ * conv1x1: out [N,ho,wo,Cout] = act(conv1x1_stride(in [N,H,W,Cin], w [Cin,Cout]) + bias (+ residual [N,ho,wo,Cout])),
+ *   stride 1 or 2, ho = (H-1)/stride+1, residual NULL for none, act = ReLU if relu != 0, Cin % 32 == 0,
+ *   Cout % 4 == 0.  All allocate temporaries and synchronise `stream`. */
+int n2nmn_resnet_debug_stem(const void *images, int is_uint8, const float *w, const float *bias,
+                            const float mean[3], float *out, int N, int H, int W, int Cout, n2nmn_stream stream);
+int n2nmn_resnet_debug_pool(const float *in, float *out, int N, int H, int W, int C, n2nmn_stream stream);
+int n2nmn_resnet_debug_conv1x1(const float *in, const float *w, const float *bias, const float *residual,
+                               float *out, int N, int H, int W, int Cin, int Cout, int stride, int relu,
+                               n2nmn_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -169,6 +169,18 @@ SYMBOLS = [
     ('n2nmn_vgg_debug_replay', _I, [_P, C.c_char_p, _I, C.POINTER(C.c_double), _P]),
     ('n2nmn_vgg_debug_conv', _I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     ('n2nmn_vgg_debug_pool', _I, [_P, _P, _I, _I, _I, _I, _P]),
+    # section 10: the ResNet-152 res5c feature extractor (a handle of its own)
+    ('n2nmn_resnet_create', _I, [_I, _I, _I, _I, C.POINTER(C.c_int), _I, C.POINTER(_P)]),
+    ('n2nmn_resnet_destroy', _I, [_P]),
+    ('n2nmn_resnet_set_mean', _I, [_P, C.POINTER(C.c_float)]),
+    ('n2nmn_resnet_set_weight', _I, [_P, C.c_char_p, _P, C.POINTER(C.c_int64), _I]),
+    ('n2nmn_resnet_commit', _I, [_P, _P]),
+    ('n2nmn_resnet_forward', _I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    ('n2nmn_resnet_get_layer', _I, [_P, C.c_char_p, _P, C.c_int64, C.POINTER(C.c_int64), _P]),
+    ('n2nmn_resnet_debug_replay', _I, [_P, C.c_char_p, _I, C.POINTER(C.c_double), _P]),
+    ('n2nmn_resnet_debug_stem', _I, [_P, _I, _P, _P, C.POINTER(C.c_float), _P, _I, _I, _I, _I, _P]),
+    ('n2nmn_resnet_debug_pool', _I, [_P, _P, _I, _I, _I, _I, _P]),
+    ('n2nmn_resnet_debug_conv1x1', _I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
 ]
 
 
