@@ -626,7 +626,7 @@ int n2nmn_train_set_moments(n2nmn_ctx *ctx, const float *m, const float *v, n2nm
 int n2nmn_get_weight(n2nmn_ctx *ctx, const char *name, float *out, n2nmn_stream stream);
 /* debug / parity: copy an internal gradient tensor ("d_word_vecs" [T_dec,N,E], "d_token_scores"
  * [T_dec,N,16], "d_encoder_outputs" [T_enc,N,L], "d_encoder_h_transformed" [T_enc,N,L],
- * "d_scores" [N,C], "token_scores" [T_dec,N,V] (the forward's token logits), "log_seq_prob" [N], N2NMN_VARIANT_SHAPES: "d_image_feat" [N,H,W,D], the gradient arriving at
+ * "d_scores" [N,C], "token_scores" [T_dec,N,V] (the forward's token logits), "log_seq_prob" [N], "dec_ctx" [T_dec,N,L] (the forward's attention context vectors), N2NMN_VARIANT_SHAPES: "d_image_feat" [N,H,W,D], the gradient arriving at
  * shapes_convnet's output) into `out` (device, capacity in floats); returns the element count */
 int64_t n2nmn_train_debug_tensor(n2nmn_ctx *ctx, const char *name, float *out, int64_t capacity,
                                  n2nmn_stream stream);
@@ -722,6 +722,8 @@ int n2nmn_debug_gemm(n2nmn_ctx *ctx, const float *A, const float *B, const float
  * setting against the oracle).  Unknown key: N2NMN_EKEY.  Keys (values are decimal strings):
  *   "tile_min_rows"  encoder steps with at most this many live rows use the K-split tiles (default 192)
  *   "eht_rows"       0: encoder_h_transform over all T N rows instead of the rows inside their length (default 1)
+ *   "dec_attn_ring"  0: the teacher-forced decoder attention keeps its 16-wave, 100 KB workgroup (one per CU) instead
+ *                    of the 8-wave, 46 KB one that shares a CU with the other stream's kernels (default 1; same bits)
  *   "profile_walk_stats" 0: profiled passes keep their event pairs but the walker kernels do not count nodes (default 1:
  *                    the counts are the families' algorithmic bytes; the atomics slow the tree-dependent launches 3 x)
  *   "debug_gemm_b3"  n2nmn_debug_gemm: n < 0 = -n launches per call (timing loops); n > 0 (n launches on the
@@ -730,6 +732,10 @@ int n2nmn_debug_gemm(n2nmn_ctx *ctx, const float *A, const float *B, const float
  *   "train_overlap"  0: no side stream (default 1)      "train_schedule" 0: every leaf after its recurrence
  *   "train_bg_wgs"   cap on background workgroups, 0 = unbounded     "train_chunks" "p0,p1,p2" time-chunk split */
 int n2nmn_debug_set(n2nmn_ctx *ctx, const char *key, const char *value);
+/* The teacher-forced decoder attention, for the A/B tests of "dec_attn_ring" (ctx may be NULL; no GPU needed):
+ * out4[0] / out4[1] = launches of the 8-wave ring kernel / of the 16-wave kernel in this process so far, out4[2] =
+ * bytes of dynamic LDS the ring kernel asks for at T_enc 45 and 20 decoder steps, out4[3] = its threads per workgroup */
+int n2nmn_debug_dec_attn(n2nmn_ctx *ctx, uint64_t *out4);
 /* out[M,N] = (relu ? max(0, .) : .)(A[M,K] . W[K,N] + bias[N]), row-major fp32, K % 4 == 0:
  * util/cnn.py:87-126 (fc_layer / fc_relu_layer) and -- on im2col rows -- the VALID strided convolutions of
  * models_shapes/shapes_convnet.py:8-17 (BASELINE.json configs[0]; not on the CLEVR hot path).  Packs W per

@@ -158,6 +158,7 @@ SYMBOLS = [
     ('n2nmn_fc_forward', _I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     ('n2nmn_crc32c', C.c_uint32, [C.c_uint32, C.c_char_p, C.c_size_t]),
     ('n2nmn_debug_set', _I, [_P, C.c_char_p, C.c_char_p]),
+    ('n2nmn_debug_dec_attn', _I, [_P, _P]),
     ('n2nmn_automaton_forces_eos', _I, [_P, _P, _P, _P, _I, _I]),
     # section 9: the VGG-16 pool5 feature extractor (a handle of its own)
     ('n2nmn_vgg_create', _I, [_I, _I, _I, _I, C.POINTER(_P)]),

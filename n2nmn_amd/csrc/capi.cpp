@@ -795,6 +795,7 @@ int decoder_impl(n2nmn_ctx* c, const n2nmn_seq2seq_io* io, hipStream_t s, const 
     a.scores = io->token_scores; a.next_idx = nullptr;
     a.Td = Td;
     a.dec_len = retire ? c->dlen : nullptr;
+    a.no_ring = knob_int(c, "dec_attn_ring", 1) == 0;
     double att_live = 1.0;             // share of the (step, row) pairs the attention evaluates
     if (retire && !dact_prof.empty()) {
       long tot = 0;
@@ -2591,10 +2592,17 @@ int n2nmn_debug_lstm_bench(n2nmn_ctx* c, int variant, int rows_per_wg, int njobs
   return check_launch("debug_lstm_bench");
 }
 
+int n2nmn_debug_dec_attn(n2nmn_ctx* ctx, uint64_t* out4) {
+  (void)ctx;
+  N2_REQUIRE(out4, N2NMN_EINVAL, "debug_dec_attn: null argument");
+  dec_attn_debug(out4);
+  return N2NMN_OK;
+}
+
 int n2nmn_debug_set(n2nmn_ctx* ctx, const char* key, const char* value) {
   N2_REQUIRE(ctx && key, N2NMN_EINVAL, "debug_set: null argument");
   static const char* const known[] = {"tile_min_rows", "eht_rows", "debug_gemm_b3", "train_overlap", "train_bg_wgs",
-                                      "train_schedule", "train_chunks", "profile_walk_stats"};
+                                      "train_schedule", "train_chunks", "profile_walk_stats", "dec_attn_ring"};
   bool ok = false;
   for (const char* k : known) ok = ok || strcmp(k, key) == 0;
   if (!ok) {

@@ -1364,6 +1364,7 @@ int64_t n2nmn_train_debug_tensor(n2nmn_ctx* c, const char* name, float* out, int
   else if (k == "d_state") { src = t->dH0; n = 4 * (int64_t)d.N * L; }
   else if (k == "token_scores") { src = t->rec.tscores; n = Td * N * d.num_vocab_nmn; }
   else if (k == "log_seq_prob") { src = t->rec.lsp; n = N; }
+  else if (k == "dec_ctx") { src = t->rec.ctx; n = Td * N * L; }          // the decoder's context vectors
   else if (k == "d_image_feat" && t->cnn_dfeat_img) { src = t->cnn_dfeat_img; n = N * d.H * d.W * d.D; }
   else {
     set_last_error("train_debug_tensor: unknown tensor '" + k + "'");

@@ -929,7 +929,9 @@ __global__ __launch_bounds__(256) void dec_attn_multi_kernel(DecStepArgs a, int 
 }
 
 // dec_attn_question_kernel: the teacher-forced attention of ONE question, ALL decoder steps, in one
-// 16-wave workgroup (nmn3_netgen_att.py:184-268 for every step at once).
+// 16-wave workgroup (nmn3_netgen_att.py:184-268 for every step at once).  Since dec_attn_ring_kernel (below)
+// this kernel runs only under n2nmn_debug_set "dec_attn_ring" = 0, or where the ring kernel's LDS request
+// does not fit 48 KB (T_enc > 64 at 20 steps): it needs a CU to itself (100 KB of LDS, 16 waves).
 // dec_attn_multi_kernel gives a question to ceil(T_dec / 4) workgroups, each of which streams the
 // question's encoder rows again (PMC: 302 MB per 512-question launch for 94 MB of rows, 170 us).  Here
 //   * the question's encoder_h_transform rows (len x 2 KB <= 92 KB) are read from HBM/L2 ONCE into LDS;
@@ -1140,6 +1142,247 @@ __global__ __launch_bounds__(1024) void dec_attn_question_kernel(DecStepArgs a, 
       if (lane < V) {
         sc = a.by[lane];
         for (int ww = 0; ww < NW; ++ww) sc += part[((size_t)ww * nsteps + j) * MAXV + lane];
+      }
+      dec_token_tail(a, n, j, (size_t)j * N + n, sc, lane);
+    }
+  }
+}
+
+// dec_attn_ring_kernel: dec_attn_question_kernel resized to share a CU -- 8 waves, <= 48 KB of LDS -- so that
+// one of its workgroups fits beside a resident lstm_tile_kernel workgroup of the other stream (64 KB, 8
+// waves), or two of them beside each other.  Same arithmetic, same summation orders, bit-identical results:
+//   * the question's len + 1 encoder_h_transform rows are STREAMED through a two-slot ring of RING_ROWS-row
+//     chunks (2 x 16 KB) instead of resting in LDS: the next chunk is requested (LDS-DMA, no registers) before
+//     the tanh work of the current one and awaited behind it, one barrier per chunk;
+//   * 8 waves = 4 step groups of SPG steps x 2 row halves (few live steps: the idle waves go to the rows);
+//     the lane <-> k map (k = 4 lane + 256 i) and wave_sum of a score are those of the 16-wave kernel;
+//   * context: a wave owns 64 columns (two 32-column MFMA blocks that share the attention fragments), the
+//     order over encoder rows per column is unchanged;
+//   * token logits: the 16 K-slices of 2L / 16 stay, one accumulator each; wave w carries slices w (fed from
+//     global `out`) and w + 8 (fed from the context rows in LDS); the slices are added in order 0..15;
+//   * the ring space later holds the context rows [nsteps][L], then -- once the token-logit MFMAs have read
+//     them -- the [16][nsteps][MAXV] partial logits.
+constexpr int RING_ROWS = 8;
+// floats of the block that is ring, then context rows, then partial logits (16 K-slices)
+__host__ __device__ constexpr int dec_ring_floats(int L, int nsteps) {
+  const int ring = 2 * RING_ROWS * L, ctx = nsteps * L, part = 16 * nsteps * MAXV;
+  return ring > ctx ? (ring > part ? ring : part) : (ctx > part ? ctx : part);
+}
+// (launch bounds: 5 waves per SIMD, i.e. at most 96 VGPRs -- two of these workgroups' waves and two of a tile
+// workgroup's fit a SIMD's 512 registers)
+constexpr int DEC_RING_THREADS = 512;
+// the limits that make the kernel fit beside a tile workgroup, at the shape the benchmark runs (T_enc 45 -> 48
+// padded score columns, 20 steps, lstm_dim 512); tests/test_dec_attn_ring_resources.py checks the VGPRs
+static_assert(DEC_RING_THREADS <= 512, "dec_attn_ring_kernel: at most 8 waves");
+static_assert(sizeof(float) * (dec_ring_floats(512, 20) + 32 * 48) <= 48 * 1024, "dec_attn_ring_kernel: at most 48 KB of LDS");
+template <int KI>
+__global__ __launch_bounds__(DEC_RING_THREADS, 5) void dec_attn_ring_kernel(DecStepArgs a, int nsteps) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  constexpr int NT = DEC_RING_THREADS, NW = NT / 64, SPG = 5, NSL = 16;
+  constexpr int RB = 4;                                      // MFMAs per operand batch and accumulator (two accumulators)
+  constexpr int RU = RING_ROWS * KI * 64 / NT;               // float4 per thread and chunk
+  const int L = a.L, T = a.T, N = a.N, V = a.V;
+  const int Tp = (T + 3) & ~3;
+  float* eS = smem;                                          // ring [2][RING_ROWS][L] -> ctx [nsteps][L] -> part
+  float* es = eS + (size_t)dec_ring_floats(L, nsteps);      // [32][Tp] scores -> attention weights
+  const int n = a.order ? a.order[blockIdx.x] : (int)blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int len = min(max(a.seq_len[n], 0), T);
+  // eos_retire: see dec_attn_question_kernel
+  const int ns = a.dec_len ? min(nsteps, max(a.dec_len[n], 0)) : nsteps;
+  if (ns < nsteps) {
+    for (int j = ns + tid; j < nsteps; j += NT) a.tokens[(size_t)j * N + n] = a.gt[(size_t)j * N + n];
+    if (ns == 0) return;
+  }
+  const bool virt = a.eht_bias && len < T;      // row `len` is the bias vector, not a row of eht
+  const int Tv = virt ? len + 1 : T;
+  const int nchunk = (Tv + RING_ROWS - 1) / RING_ROWS;
+
+  // ---- 0./1. e[j][tau] = sum_k v_k tanh(q_j,k + eht[tau, n, k]), rows through the ring     (:184-187)
+  {
+    // chunk c -> its ring slot by LDS-DMA, no registers: a wave instruction copies 1 KB = half a row, so the
+    // source row is wave-uniform; rows past Tv - 1 repeat that row (never scored)
+    const int wu = __builtin_amdgcn_readfirstlane(w);
+    const uint32_t lds0 = (uint32_t)(uintptr_t)smem;
+    auto fetch = [&](int c) {
+#pragma unroll
+      for (int u = 0; u < RU; ++u) {
+        const int piece = wu + u * NW;                        // 1 KB piece of the chunk
+        const int row = min(c * RING_ROWS + piece / KI, Tv - 1);
+        const float* er = (virt && row == len) ? a.eht_bias : a.eht + ((size_t)row * N + n) * L;
+        glds16(er, (uint32_t)((piece % KI) * 1024 + 16 * lane),
+               lds0 + (uint32_t)(c & 1) * (uint32_t)(RING_ROWS * L * sizeof(float)) + (uint32_t)piece * 1024u);
+      }
+    };
+    fetch(0);
+    const int nrq = ns > 2 * SPG ? 2 : (ns > SPG ? 4 : 8);   // row parts
+    const int sg = w / nrq, tq = w - sg * nrq;
+    const int j0 = sg * SPG;
+    float4 v4[KI], q4[SPG][KI];
+#pragma unroll
+    for (int i = 0; i < KI; ++i) {
+      const int k = 4 * lane + 256 * i;
+      v4[i] = *reinterpret_cast<const float4*>(a.v + k);
+#pragma unroll
+      for (int j = 0; j < SPG; ++j) {
+        const int jj = min(j0 + j, ns - 1);
+        q4[j][i] = *reinterpret_cast<const float4*>(a.q + ((size_t)jj * N + n) * L + k);
+      }
+    }
+    for (int i = tid; i < 32 * Tp; i += NT) es[i] = 0.f;
+    wait_vm<0>();                                            // (the DMA is not counted by the compiler)
+    __syncthreads();
+    for (int c = 0; c < nchunk; ++c) {
+      if (c + 1 < nchunk) fetch(c + 1);
+      const float* slot = eS + (size_t)(c & 1) * RING_ROWS * L;
+      const int tau_c = c * RING_ROWS;
+      const int cn = min(RING_ROWS, Tv - tau_c);             // rows of this chunk
+      if (j0 < ns) {
+        // one row per trip: the two-row trip of the 16-wave kernel costs 14 more VGPRs, which is the
+        // difference between 5 and 4 waves per SIMD here; a score is the same sum either way
+        for (int r = tq; r < cn; r += nrq) {
+          float4 e0[KI];
+#pragma unroll
+          for (int i = 0; i < KI; ++i)
+            e0[i] = *reinterpret_cast<const float4*>(slot + (size_t)r * L + 4 * lane + 256 * i);
+#pragma unroll
+          for (int j = 0; j < SPG; ++j) {
+            float s0 = 0.f;
+#pragma unroll
+            for (int i = 0; i < KI; ++i)
+              s0 += v4[i].x * fast_tanh(q4[j][i].x + e0[i].x) + v4[i].y * fast_tanh(q4[j][i].y + e0[i].y) +
+                    v4[i].z * fast_tanh(q4[j][i].z + e0[i].z) + v4[i].w * fast_tanh(q4[j][i].w + e0[i].w);
+            const float r0s = wave_sum(s0);
+            if (lane == 0 && j0 + j < ns) es[(j0 + j) * Tp + tau_c + r] = r0s;
+          }
+        }
+      }
+      wait_vm<0>();                                          // this wave's pieces of chunk c + 1 have landed
+      __syncthreads();
+    }
+  }
+  if (virt && len + 1 < T) {
+    const int rest = T - len - 1;
+    for (int i = tid; i < ns * rest; i += NT) {
+      const int j = i / rest, tau = len + 1 + i - j * rest;
+      es[j * Tp + tau] = es[j * Tp + len];
+    }
+    __syncthreads();
+  }
+  // ---- 2. softmax over ALL T rows, mask finished rows, renormalise                   (:190-191)
+  for (int j = w; j < ns; j += NW) {
+    float* ej = es + j * Tp;
+    float m = -INFINITY;
+    for (int tau = lane; tau < T; tau += 64) m = fmaxf(m, ej[tau]);
+    m = wave_max(m);
+    float sm = 0.f;
+    for (int tau = lane; tau < T; tau += 64) sm += expf(ej[tau] - m);
+    sm = wave_sum(sm);
+    float s2 = 0.f;
+    for (int tau = lane; tau < T; tau += 64) {
+      float p = expf(ej[tau] - m) / sm;
+      p = tau < len ? p : 0.f;
+      ej[tau] = p;
+      s2 += p;
+    }
+    s2 = wave_sum(s2);
+    float* arow = a.atts + (size_t)j * T * N;
+    for (int tau = lane; tau < T; tau += 64) {
+      const float att = ej[tau] / s2;
+      ej[tau] = att;
+      arow[(size_t)tau * N + n] = att;
+    }
+  }
+  __syncthreads();
+  // ---- 3. ctx[j] = sum_tau att[j][tau] * eout[tau, n, :]  on the matrix cores          (:193)
+  // as in dec_attn_question_kernel; the two 32-column blocks of a wave share the A fragments
+  {
+    float* ctxS = eS;                                        // every wave is done with the ring
+    const int li = lane & 31, kh = lane >> 5;
+    const int nm = (len + 1) >> 1;                           // MFMAs (2 encoder rows each)
+    for (int cb = 64 * w; cb < L; cb += 64 * NW) {
+      f32x16 acc0, acc1;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
+      // (uniform base + 32-bit lane offsets: T N L < 2^30 is the launcher's condition)
+      const float* bcol = a.eout + (size_t)n * L + cb;
+      for (int m0 = 0; m0 < nm; m0 += RB) {
+        float b0[RB], b1[RB], av[RB];
+#pragma unroll
+        for (int u = 0; u < RB; ++u) {
+          const uint32_t tau = min(2 * (m0 + u) + kh, T - 1);
+          b0[u] = bcol[tau * (uint32_t)(N * L) + li];
+          b1[u] = bcol[tau * (uint32_t)(N * L) + li + 32];
+          av[u] = es[li * Tp + min(2 * (m0 + u) + kh, Tp - 1)];
+        }
+#pragma unroll
+        for (int u = 0; u < RB; ++u)
+          if (m0 + u < nm) {
+            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], b0[u], acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], b1[u], acc1, 0, 0, 0);
+          }
+      }
+      // C/D layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int j = (r & 3) + 8 * (r >> 2) + 4 * kh;
+        if (j < ns) {
+          ctxS[(size_t)j * L + cb + li] = acc0[r];
+          ctxS[(size_t)j * L + cb + 32 + li] = acc1[r];
+          if (a.ctx_out) {
+            a.ctx_out[(uint32_t)((j * N + n) * L + cb + li)] = acc0[r];
+            a.ctx_out[(uint32_t)((j * N + n) * L + cb + 32 + li)] = acc1[r];
+          }
+        }
+      }
+    }
+  }
+  __syncthreads();
+  // ---- 4. token logits = [out, ctx] . W_y + b_y for all steps: one [32 x 2L] x [2L x 32] product on
+  // the matrix cores, K split into NSL slices, two per wave                              (:196-198)
+  {
+    const float* ctxS = eS;
+    float* part = eS;                                        // [NSL][nsteps][MAXV], over the ctx rows once read
+    const int li = lane & 31, kh = lane >> 5;
+    const int kper = 2 * L / NSL;                            // k range of a slice (64 at L = 512)
+    const int jr = min(li, ns - 1);
+    f32x16 acc[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[h][r] = 0.f;
+    for (int m0 = 0; m0 < kper / 2; m0 += RB) {
+      float av[2][RB], bv[2][RB];
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int u = 0; u < RB; ++u) {
+          const int k = (w + NW * h) * kper + 2 * (m0 + u) + kh;
+          av[h][u] = k < L ? a.out[(uint32_t)((jr * N + n) * L + k)] : ctxS[jr * L + k - L];
+          bv[h][u] = li < V ? a.Wy[(uint32_t)(k * V + li)] : 0.f;
+        }
+#pragma unroll
+      for (int u = 0; u < RB; ++u)
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+          acc[h] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[h][u], bv[h][u], acc[h], 0, 0, 0);
+    }
+    __syncthreads();                                         // the ctx rows are read: part may take their place
+    if (li < MAXV) {
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int j = (r & 3) + 8 * (r >> 2) + 4 * kh;     // step (row of D), li = token (column)
+          if (j < ns) part[((size_t)(w + NW * h) * nsteps + j) * MAXV + li] = acc[h][r];
+        }
+    }
+    __syncthreads();
+    for (int j = w; j < ns; j += NW) {
+      float sc = -INFINITY;
+      if (lane < V) {
+        sc = a.by[lane];
+        for (int ww = 0; ww < NSL; ++ww) sc += part[((size_t)ww * nsteps + j) * MAXV + lane];
       }
       dec_token_tail(a, n, j, (size_t)j * N + n, sc, lane);
     }
@@ -1614,15 +1857,37 @@ static void launch_dec_multi(const DecStepArgs& a, int nsteps, hipStream_t s) {
                      smem, s, a, nsteps);
 }
 
+// dynamic LDS of dec_attn_ring_kernel: the ring / context block and the [32][Tp] scores
+static size_t dec_ring_lds_bytes(int T, int L, int nsteps) {
+  return sizeof(float) * ((size_t)dec_ring_floats(L, nsteps) + 32 * (size_t)((T + 3) & ~3));
+}
+// launches of the two per-question kernels in this process (n2nmn_debug_dec_attn: the A/B tests prove which ran)
+static std::atomic<uint64_t> g_dec_ring_launches{0}, g_dec_question_launches{0};
+void dec_attn_debug(uint64_t out[4]) {
+  out[0] = g_dec_ring_launches.load();
+  out[1] = g_dec_question_launches.load();
+  out[2] = dec_ring_lds_bytes(45, 512, 20);
+  out[3] = DEC_RING_THREADS;
+}
+
 template <int KI>
 static bool launch_dec_question(const DecStepArgs& a, int nsteps, hipStream_t s) {
   const int Tp = (a.T + 3) & ~3;
   const size_t smem = sizeof(float) * ((size_t)std::max(a.T, nsteps) * a.L + 32 * (size_t)Tp + 16 * 4 * MAXV);
   if (smem > 150 * 1024 || (size_t)a.T * a.L > (size_t)3 * KI * 4096 ||
       (size_t)nsteps * (a.L + 16 * MAXV) > (size_t)std::max(a.T, nsteps) * a.L) return false;
+  // the 8-wave ring form shares a CU with the other stream's workgroups (DecStepArgs::no_ring: the A/B switch)
+  const size_t ring = dec_ring_lds_bytes(a.T, a.L, nsteps);
+  if (!a.no_ring && a.L == 256 * KI && ring <= 48 * 1024 &&
+      (size_t)std::max(a.T, nsteps) * a.N * a.L < ((size_t)1 << 30)) {      // (32-bit lane offsets)
+    hipLaunchKernelGGL((dec_attn_ring_kernel<KI>), dim3(a.N), dim3(DEC_RING_THREADS), ring, s, a, nsteps);
+    ++g_dec_ring_launches;
+    return true;
+  }
   static std::atomic<uint64_t> attr{0};
   ensure_dynamic_lds(reinterpret_cast<const void*>(dec_attn_question_kernel<KI>), 150 * 1024, attr);
   hipLaunchKernelGGL((dec_attn_question_kernel<KI>), dim3(a.N), dim3(1024), smem, s, a, nsteps);
+  ++g_dec_question_launches;
   return true;
 }
 
