@@ -92,6 +92,21 @@ const char *n2nmn_version(void);
 /* ------------------------------------------------------------------------------------------
  * (1) context, weights.   Replaces: tf.Session + tf.get_variable + tf.train.Saver.restore
  *     (exp_clevr/eval_clevr.py:18-20,90-91; models_clevr/nmn3_modules.py:11-47).
+ *
+ *     Accepted dimensions (anything else: N2NMN_EINVAL and a message naming the field):
+ *       lstm_dim        a multiple of 128, at most 1024 (the decoder attention kernels keep a lane's
+ *                       columns in four float4 registers at a stride of 256)
+ *       map_dim         1 .. 1024;  D  a multiple of 16, at most 4096
+ *       embed_dim_txt   a multiple of 4, equal to embed_dim_nmn
+ *       kernel_size     3 or 5;  num_vocab_nmn  2 .. 16 (training: at most 15);  num_layers  2
+ *       H, W, num_choices, N, T_encoder, T_decoder, num_vocab_txt   positive, with
+ *                       T_encoder * embed_dim_txt + T_decoder * T_encoder <= 16000
+ *     Inside that space a context computes what the fp64 oracle computes (tests/test_gpu_dims_sweep.py).
+ *     Narrower limits decide routes, not acceptance: n2nmn_walk_supported (D / 4 divides 512, at most
+ *     38 feature rows per thread, num_choices <= 512, H * W <= 192, map_dim * num_choices <= 65536,
+ *     150 KB of LDS) picks the layout walker or the level path for n2nmn_execute_tokens; inside the walker,
+ *     deferred pooling needs D % 32 == 0 and the staged form num_choices <= 256.  n2nmn_train_enable
+ *     refuses H * W > 192 and map_dim * num_choices > 65536 in the CLEVR variant.
  * ---------------------------------------------------------------------------------------- */
 int n2nmn_ctx_create(const n2nmn_dims *dims, int device, n2nmn_ctx **out);
 /* A second context on the same device that SHARES the weight store of `parent` (committed through

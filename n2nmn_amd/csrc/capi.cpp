@@ -1560,9 +1560,21 @@ const char* n2nmn_version(void) { return "n2nmn-mi355x 0.1 (gfx950)"; }
 int n2nmn_ctx_create(const n2nmn_dims* dims, int device, n2nmn_ctx** out) {
   N2_REQUIRE(dims && out, N2NMN_EINVAL, "ctx_create: null argument");
   const n2nmn_dims& d = *dims;
+  {
+    // first of all: the kernels divide by these (D / 4 columns, H * W rows, ...), and a zero is a multiple of anything
+    const struct { const char* name; int32_t v; } pos[] = {
+        {"H", d.H}, {"W", d.W}, {"D", d.D}, {"map_dim", d.map_dim}, {"embed_dim_txt", d.embed_dim_txt},
+        {"embed_dim_nmn", d.embed_dim_nmn}, {"lstm_dim", d.lstm_dim}, {"num_vocab_txt", d.num_vocab_txt},
+        {"num_choices", d.num_choices}, {"T_encoder", d.T_encoder}, {"T_decoder", d.T_decoder}, {"N", d.N}};
+    for (const auto& f : pos)
+      N2_REQUIRE(f.v > 0, N2NMN_EINVAL, std::string("ctx_create: ") + f.name + " must be positive");
+  }
   N2_REQUIRE(d.num_layers == 2, N2NMN_EINVAL, "ctx_create: only num_layers == 2 is supported");
   N2_REQUIRE(d.lstm_dim > 0 && d.lstm_dim % 128 == 0, N2NMN_EINVAL,
              "ctx_create: lstm_dim must be a multiple of 128");
+  // the decoder attention kernels (dec_attn_kernel, dec_bwd_a_kernel) hold the lstm_dim columns of a
+  // lane in MAXKI = 4 float4 registers at a stride of 256: columns from 1024 upward would be skipped
+  N2_REQUIRE(d.lstm_dim <= 1024, N2NMN_EINVAL, "ctx_create: lstm_dim must be <= 1024");
   N2_REQUIRE(d.embed_dim_txt % 4 == 0 && d.embed_dim_nmn == d.embed_dim_txt, N2NMN_EINVAL,
              "ctx_create: embed dims must be equal multiples of 4");
   N2_REQUIRE(d.D % (4 * POOL_PARTS) == 0 && d.D <= 4096, N2NMN_EINVAL,
@@ -1576,9 +1588,6 @@ int n2nmn_ctx_create(const n2nmn_dims* dims, int device, n2nmn_ctx** out) {
              "ctx_create: kernel_size must be 3 or 5");
   N2_REQUIRE(d.num_vocab_nmn >= 2 && d.num_vocab_nmn <= 16, N2NMN_EINVAL,
              "ctx_create: num_vocab_nmn must be in [2, 16]");
-  N2_REQUIRE(d.H > 0 && d.W > 0 && d.map_dim > 0 && d.num_choices > 0 && d.N > 0 &&
-                 d.T_encoder > 0 && d.T_decoder > 0 && d.num_vocab_txt > 0,
-             N2NMN_EINVAL, "ctx_create: non-positive dimension");
   N2_REQUIRE((size_t)d.T_encoder * d.embed_dim_txt + (size_t)d.T_decoder * d.T_encoder <= 16000,
              N2NMN_EINVAL, "ctx_create: T_encoder*embed_dim_txt too large for the LDS staging");
   n2nmn_ctx* c = new (std::nothrow) n2nmn_ctx();
@@ -2243,7 +2252,7 @@ int n2nmn_walk_layouts(n2nmn_ctx* c, const n2nmn_walk_batch* batches, int K, int
   // staged walker: with both of the above the tree-dependent work leaves the one-workgroup-per-question
   // chain too (kernels_walk.hip: walk_heavy_kernel / walk_fspepi_kernel / walk_light_kernel); n2nmn_walk_set_staged(ctx, 0)
   // keeps the round-3 walker
-  const bool staged = pre && a.defer_pool && c->walk_staged != 0 &&
+  const bool staged = pre && a.defer_pool && c->walk_staged != 0 && walk_staged_supported(d.num_choices) &&
                       K * N < (1 << 22) && T_dec <= 255;
   if (a.defer_pool) {
     // the per-pass counters (two sets, used alternately: walk_fcatt_kernel clears the other one) and the

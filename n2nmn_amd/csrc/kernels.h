@@ -470,6 +470,8 @@ void launch_walk_light(const ModuleWeights& w, const WalkArgs& a, hipStream_t s)
 void launch_walk_pool(const ModuleWeights& w, const WalkArgs& a, hipStream_t s);
 void launch_walk_heads(const ModuleWeights& w, const WalkArgs& a, hipStream_t s);
 int walk_pool_supported(int H, int W, int D);
+// walk_light_kernel (the staged walker's answer heads) runs 256 threads and gives every logit a thread
+int walk_staged_supported(int C);
 
 // out[n,h,w,:] = [feat[n,h,w,:D0], linspace(-1,1,W)[w], linspace(-1,1,H)[h], 0 ...]
 void launch_add_coords(const float* feat, int N, int H, int W, int D0, int D, float* out,

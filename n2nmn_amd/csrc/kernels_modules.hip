@@ -467,10 +467,13 @@ __device__ void pool_item(const ModuleWeights& w, const ModuleBuffers& b, int ta
   const float* fp = b.feat + (size_t)nd.n * HW * D + c0 + 4 * lc;
   float4 fr[PR];
   if (regpath) {
+    // (a thread without rows -- lr >= H*W at small maps, or lr >= nrow where MT % ncol != 0 -- still
+    // loads: from a row of the image, never from behind it)
+    const int lr_in = min(lr, HW - 1);
 #pragma unroll
     for (int q = 0; q < PR; ++q) {
       const int r = lr + q * nrow;
-      fr[q] = *reinterpret_cast<const float4*>(fp + (size_t)(q < myrows ? r : lr) * D);
+      fr[q] = *reinterpret_cast<const float4*>(fp + (size_t)(q < myrows ? r : lr_in) * D);
     }
   }
   __builtin_amdgcn_sched_barrier(0);

@@ -386,6 +386,7 @@ __device__ void find_epilogue_bwd(const ModuleWeights& w, const ModuleBuffers& b
 #pragma unroll
       for (int i = 0; i < MAXCI; ++i) {
         const int c = 4 * lane + 256 * i;
+        float4 dm4 = make_float4(0.f, 0.f, 0.f, 0.f);   // d M[r, c .. c + 3]
         if (c < Mp) {
           const float p0 = m4[i].x * t4[i].x, p1 = m4[i].y * t4[i].y, p2 = m4[i].z * t4[i].z,
                       p3 = m4[i].w * t4[i].w;
@@ -394,20 +395,22 @@ __device__ void find_epilogue_bwd(const ModuleWeights& w, const ModuleBuffers& b
           dwe[i].x += ka * p0; dwe[i].y += ka * p1; dwe[i].z += ka * p2; dwe[i].w += ka * p3;
           dtt[i].x += d0 * m4[i].x; dtt[i].y += d1 * m4[i].y; dtt[i].z += d2 * m4[i].z;
           dtt[i].w += d3 * m4[i].w;
-          if (gr != 0.f) {                            // wave-uniform
-            // several nodes may share a conv_image slab -> atomic adds; a lane holds 4 consecutive
-            // channels, so adding them directly is four 16-B-strided atomics (8 cache lines each,
-            // 30 of the kernel's 51 us): transposed through LDS each atomic covers 64 consecutive
-            // channels (2 lines)
-            *reinterpret_cast<float4*>(xp + 4 * lane) =
-                make_float4(d0 * t4[i].x, d1 * t4[i].y, d2 * t4[i].z, d3 * t4[i].w);
-            float* dm = dMbuf + (size_t)r * Mp + 256 * i;
+          dm4 = make_float4(d0 * t4[i].x, d1 * t4[i].y, d2 * t4[i].z, d3 * t4[i].w);
+        }
+        if (gr != 0.f && 256 * i < Mp) {              // wave-uniform
+          // several nodes may share a conv_image slab -> atomic adds; a lane holds 4 consecutive
+          // channels, so adding them directly is four 16-B-strided atomics (8 cache lines each,
+          // 30 of the kernel's 51 us): transposed through LDS each atomic covers 64 consecutive
+          // channels (2 lines).  EVERY lane takes part in the transposed half: lane l adds the
+          // channels l, l + 64, ..., whichever lanes computed them -- with Mp % 256 != 0 the lanes
+          // whose own four channels lie beyond Mp still own channels below it
+          *reinterpret_cast<float4*>(xp + 4 * lane) = dm4;
+          float* dm = dMbuf + (size_t)r * Mp + 256 * i;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-              const int cc = lane + 64 * k;
-              const float v = xp[cc];
-              if (256 * i + cc < M) atomicAdd(dm + cc, v);
-            }
+          for (int k = 0; k < 4; ++k) {
+            const int cc = lane + 64 * k;
+            const float v = xp[cc];
+            if (256 * i + cc < M) atomicAdd(dm + cc, v);
           }
         }
       }

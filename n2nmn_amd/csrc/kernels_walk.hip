@@ -2214,6 +2214,11 @@ int walk_pool_supported(int H, int W, int D) {
   return (H * W + nrow - 1) / nrow <= WALK_POOLK_ROWS;
 }
 
+// light_item<HT>: fc_out_t splits HT / C feature slices over the threads and thread c < HT writes logit c, so
+// beyond HT choices no slice is left and the logits from HT upward have no writer: such contexts keep the
+// one-workgroup walker (WT = 512 threads, C <= WT by walk_supported)
+int walk_staged_supported(int C) { return C <= HT; }
+
 int walk_supported(int H, int W, int D, int M, int Mp, int HWp, int E, int C, int T, int ksize,
                    int T_enc) {
   const int HW = H * W;
