@@ -737,8 +737,6 @@ int n2nmn_debug_gemm(n2nmn_ctx *ctx, const float *A, const float *B, const float
  * setting against the oracle).  Unknown key: N2NMN_EKEY.  Keys (values are decimal strings):
  *   "tile_min_rows"  encoder steps with at most this many live rows use the K-split tiles (default 192)
  *   "eht_rows"       0: encoder_h_transform over all T N rows instead of the rows inside their length (default 1)
- *   "dec_attn_ring"  0: the teacher-forced decoder attention keeps its 16-wave, 100 KB workgroup (one per CU) instead
- *                    of the 8-wave, 46 KB one that shares a CU with the other stream's kernels (default 1; same bits)
  *   "profile_walk_stats" 0: profiled passes keep their event pairs but the walker kernels do not count nodes (default 1:
  *                    the counts are the families' algorithmic bytes; the atomics slow the tree-dependent launches 3 x)
  *   "debug_gemm_b3"  n2nmn_debug_gemm: n < 0 = -n launches per call (timing loops); n > 0 (n launches on the
@@ -747,9 +745,9 @@ int n2nmn_debug_gemm(n2nmn_ctx *ctx, const float *A, const float *B, const float
  *   "train_overlap"  0: no side stream (default 1)      "train_schedule" 0: every leaf after its recurrence
  *   "train_bg_wgs"   cap on background workgroups, 0 = unbounded     "train_chunks" "p0,p1,p2" time-chunk split */
 int n2nmn_debug_set(n2nmn_ctx *ctx, const char *key, const char *value);
-/* The teacher-forced decoder attention, for the A/B tests of "dec_attn_ring" (ctx may be NULL; no GPU needed):
- * out4[0] / out4[1] = launches of the 8-wave ring kernel / of the 16-wave kernel in this process so far, out4[2] =
- * bytes of dynamic LDS the ring kernel asks for at T_enc 45 and 20 decoder steps, out4[3] = its threads per workgroup */
+/* The teacher-forced decoder attention, for its tests (ctx may be NULL; no GPU needed): out4[0] = launches of the
+ * 8-wave ring kernel in this process so far, out4[1] = reserved, always 0, out4[2] = bytes of dynamic LDS the ring
+ * kernel asks for at T_enc 45 and 20 decoder steps, out4[3] = its threads per workgroup */
 int n2nmn_debug_dec_attn(n2nmn_ctx *ctx, uint64_t *out4);
 /* out[M,N] = (relu ? max(0, .) : .)(A[M,K] . W[K,N] + bias[N]), row-major fp32, K % 4 == 0:
  * util/cnn.py:87-126 (fc_layer / fc_relu_layer) and -- on im2col rows -- the VALID strided convolutions of

@@ -617,7 +617,7 @@ int decoder_impl(n2nmn_ctx* c, const n2nmn_seq2seq_io* io, hipStream_t s, const 
   // ---- eos_retire (N2NMN_S2S_EOS_RETIRE, include/n2nmn.h): rows leave the decoder at their layout's first
   // <eos>.  Preconditions: an inference pass of >= 128 rows in a throughput mode (the tile kernels take the
   // rows in ranked order and a device-side live count), nothing fetched that needs the dead steps.
-  a.q = c->qbuf; a.out = c->dec_h1_all; a.gt = io->gt_layout; a.Td = Td;     // (dec_question_supported reads these)
+  a.q = c->qbuf; a.out = c->dec_h1_all; a.gt = io->gt_layout; a.Td = Td;     // (dec_len_supported reads `a`)
   const bool retire = batched && (io->flags & N2NMN_S2S_EOS_RETIRE) &&
                       !c->rec && !io->drop_dec0 && !io->token_scores &&
                       lstm_wide(c) >= 2 && N >= 128 && Td <= 63 && root(c)->have_token_ops &&
@@ -795,7 +795,6 @@ int decoder_impl(n2nmn_ctx* c, const n2nmn_seq2seq_io* io, hipStream_t s, const 
     a.scores = io->token_scores; a.next_idx = nullptr;
     a.Td = Td;
     a.dec_len = retire ? c->dlen : nullptr;
-    a.no_ring = knob_int(c, "dec_attn_ring", 1) == 0;
     double att_live = 1.0;             // share of the (step, row) pairs the attention evaluates
     if (retire && !dact_prof.empty()) {
       long tot = 0;
@@ -2611,7 +2610,7 @@ int n2nmn_debug_dec_attn(n2nmn_ctx* ctx, uint64_t* out4) {
 int n2nmn_debug_set(n2nmn_ctx* ctx, const char* key, const char* value) {
   N2_REQUIRE(ctx && key, N2NMN_EINVAL, "debug_set: null argument");
   static const char* const known[] = {"tile_min_rows", "eht_rows", "debug_gemm_b3", "train_overlap", "train_bg_wgs",
-                                      "train_schedule", "train_chunks", "profile_walk_stats", "dec_attn_ring"};
+                                      "train_schedule", "train_chunks", "profile_walk_stats"};
   bool ok = false;
   for (const char* k : known) ok = ok || strcmp(k, key) == 0;
   if (!ok) {

@@ -211,12 +211,9 @@ struct DecStepArgs {
   float* scores;           // [steps][N][V] or nullptr
   int32_t* next_idx;       // [N] row of the decoder x-table for the next step (= token) or nullptr
   float* ctx_out;          // [steps][N][L] context vectors kept for the backward pass, or nullptr
-  // eos_retire (teacher-forced passes: dec_attn_question_kernel / dec_attn_multi_kernel): live decoder steps per question;
+  // eos_retire (teacher-forced passes: dec_attn_ring_kernel / dec_attn_multi_kernel): live decoder steps per question;
   // steps at or past it get their token from `gt` and nothing else.  nullptr: every step of every question
   const int32_t* dec_len;  // [N]
-  // n2nmn_debug_set "dec_attn_ring" = 0: keep the 16-wave dec_attn_question_kernel where the 8-wave
-  // dec_attn_ring_kernel would serve the launch (same results, bit for bit)
-  int no_ring;
   // eos_retire, sequential decoding (dec_attn_seq_kernel; dec_compact_kernel builds these after every step):
   // workgroup j serves original row live_perm[j]; j >= *live_n: the row has emitted <eos> and gets eos_token.
   // q is read at state row j, every other operand by original row.  nullptr: all rows live, identity
@@ -281,11 +278,10 @@ struct BeamBacktrackArgs {
   int K, N, T, Td;
 };
 void launch_beam_backtrack(const BeamBacktrackArgs& a, hipStream_t s);
-// can launch_dec_attn serve this launch with dec_attn_question_kernel (the kernel that honours dec_len)?
-bool dec_question_supported(const DecStepArgs& a, int nsteps);
+// does launch_dec_attn serve this teacher-forced launch with a kernel that honours dec_len?
 bool dec_len_supported(const DecStepArgs& a, int nsteps);
-// n2nmn_debug_dec_attn: launches of dec_attn_ring_kernel / dec_attn_question_kernel so far, the ring kernel's
-// dynamic LDS request at T_enc 45 and 20 steps, its threads per workgroup
+// n2nmn_debug_dec_attn: launches of dec_attn_ring_kernel so far, 0 (reserved), the ring kernel's dynamic LDS
+// request at T_enc 45 and 20 steps, its threads per workgroup
 void dec_attn_debug(uint64_t out[4]);
 // eos_retire helpers (kernels_seq2seq.hip): layout lengths from the tokens; state rows gathered by `perm`
 bool dec_seq_retire_supported(const DecStepArgs& a);

@@ -928,238 +928,26 @@ __global__ __launch_bounds__(256) void dec_attn_multi_kernel(DecStepArgs a, int 
   }
 }
 
-// dec_attn_question_kernel: the teacher-forced attention of ONE question, ALL decoder steps, in one
-// 16-wave workgroup (nmn3_netgen_att.py:184-268 for every step at once).  Since dec_attn_ring_kernel (below)
-// this kernel runs only under n2nmn_debug_set "dec_attn_ring" = 0, or where the ring kernel's LDS request
-// does not fit 48 KB (T_enc > 64 at 20 steps): it needs a CU to itself (100 KB of LDS, 16 waves).
-// dec_attn_multi_kernel gives a question to ceil(T_dec / 4) workgroups, each of which streams the
-// question's encoder rows again (PMC: 302 MB per 512-question launch for 94 MB of rows, 170 us).  Here
-//   * the question's encoder_h_transform rows (len x 2 KB <= 92 KB) are read from HBM/L2 ONCE into LDS;
-//   * the tanh scores e[j][tau] = sum_k v_k tanh(q_j,k + eht[tau,k]) -- the VALU-bound part, two
-//     transcendentals per (step, row, k) -- are spread over the 16 waves as 4 step groups x 4 row
-//     quarters: a wave keeps the query vectors of its 5 steps in registers and walks its rows in LDS;
-//   * the context vectors ctx[j] = sum_tau att[j][tau] eout[tau] are ONE small matrix product per
-//     question ([32 steps] x [len] x [L]) on the matrix cores (v_mfma_f32_32x32x2_f32): every wave owns
-//     32 (64) columns, its B fragments are the encoder_outputs rows straight from global memory, each
-//     element loaded exactly once, the attention weights come from LDS;
-//   * token logits, validity, probabilities and entropy as in the other two kernels (dec_token_tail).
-template <int KI>
-__global__ __launch_bounds__(1024) void dec_attn_question_kernel(DecStepArgs a, int nsteps) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  constexpr int NT = 1024, NW = 16, SPG = 5;
-  const int L = a.L, T = a.T, N = a.N, V = a.V;
-  const int Tp = (T + 3) & ~3;
-  float* eS = smem;                                          // [max(T, nsteps)][L]: eht rows, later ctx
-  float* es = eS + (size_t)(T > nsteps ? T : nsteps) * L;   // [32][Tp] scores -> attention weights
-  // work per question grows with its length (5..45 rows): the longest questions take the lowest
-  // workgroup ids, i.e. are dispatched first, and the short ones fill in behind them
-  const int n = a.order ? a.order[blockIdx.x] : (int)blockIdx.x;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int len = min(max(a.seq_len[n], 0), T);
-  // eos_retire (DecStepArgs::dec_len): only the steps that emit a module token are evaluated -- the steps
-  // from the first <eos> on feed nothing the caller asked for (decoder_impl); their tokens are the given
-  // ones.  `nsteps` keeps describing the launch (LDS layout, output strides), `ns` the work.
-  const int ns = a.dec_len ? min(nsteps, max(a.dec_len[n], 0)) : nsteps;
-  if (ns < nsteps) {
-    for (int j = ns + tid; j < nsteps; j += NT) a.tokens[(size_t)j * N + n] = a.gt[(size_t)j * N + n];
-    if (ns == 0) return;
-  }
-  // rows past the question's length all equal the bias of encoder_h_transform: virtual row `len`
-  // stands for every one of them (evaluated once, copied to the others below)
-  const bool virt = a.eht_bias && len < T;      // row `len` is the bias vector, not a row of eht
-  const int Tv = virt ? len + 1 : T;
-
-  // ---- 0. the question's rows -> LDS (16 KB per sweep of the workgroup), zero the score block -----
-  {
-    const int ncol = L / 4, total = Tv * ncol;
-    constexpr int SW = 3 * KI;                               // sweeps cover T * L <= 12 K * KI floats
-    float4 r4[SW];
-#pragma unroll
-    for (int u = 0; u < SW; ++u) {
-      const int i = min(tid + u * NT, total - 1);
-      const int row = i / ncol, c4 = i - row * ncol;
-      const float* er = (virt && row == len) ? a.eht_bias : a.eht + ((size_t)row * N + n) * L;
-      r4[u] = *reinterpret_cast<const float4*>(er + 4 * c4);
-    }
-#pragma unroll
-    for (int u = 0; u < SW; ++u) {
-      const int i = tid + u * NT;
-      if (i < total) *reinterpret_cast<float4*>(eS + 4 * (size_t)i) = r4[u];
-    }
-    for (int i = tid; i < 32 * Tp; i += NT) es[i] = 0.f;
-  }
-  __syncthreads();
-  // ---- 1. e[j][tau] = sum_k v_k tanh(q_j,k + eht[tau, n, k])                          (:184-187)
-  {
-    // 16 waves = (step groups of SPG steps) x (row parts): four groups x four row quarters for a full
-    // launch; a question with few live steps (eos_retire) gives its waves to the rows instead
-    const int nrq = ns > 2 * SPG ? 4 : (ns > SPG ? 8 : 16);  // row parts
-    const int sg = w / nrq, tq = w - sg * nrq;
-    const int j0 = sg * SPG;
-    float4 v4[KI], q4[SPG][KI];
-#pragma unroll
-    for (int i = 0; i < KI; ++i) {
-      const int k = 4 * lane + 256 * i;
-      v4[i] = *reinterpret_cast<const float4*>(a.v + k);
-#pragma unroll
-      for (int j = 0; j < SPG; ++j) {
-        const int jj = min(j0 + j, ns - 1);
-        q4[j][i] = *reinterpret_cast<const float4*>(a.q + ((size_t)jj * N + n) * L + k);
-      }
-    }
-    if (j0 < ns) {
-      for (int tau = tq; tau < Tv; tau += 2 * nrq) {         // two rows of this part per trip
-        const int tau1 = tau + nrq;
-        float4 e0[KI], e1[KI];
-#pragma unroll
-        for (int i = 0; i < KI; ++i) {
-          e0[i] = *reinterpret_cast<const float4*>(eS + (size_t)tau * L + 4 * lane + 256 * i);
-          e1[i] = *reinterpret_cast<const float4*>(eS + (size_t)min(tau1, Tv - 1) * L + 4 * lane + 256 * i);
-        }
-#pragma unroll
-        for (int j = 0; j < SPG; ++j) {
-          float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-          for (int i = 0; i < KI; ++i) {
-            s0 += v4[i].x * fast_tanh(q4[j][i].x + e0[i].x) + v4[i].y * fast_tanh(q4[j][i].y + e0[i].y) +
-                  v4[i].z * fast_tanh(q4[j][i].z + e0[i].z) + v4[i].w * fast_tanh(q4[j][i].w + e0[i].w);
-            s1 += v4[i].x * fast_tanh(q4[j][i].x + e1[i].x) + v4[i].y * fast_tanh(q4[j][i].y + e1[i].y) +
-                  v4[i].z * fast_tanh(q4[j][i].z + e1[i].z) + v4[i].w * fast_tanh(q4[j][i].w + e1[i].w);
-          }
-          const float r0 = wave_sum(s0), r1 = wave_sum(s1);
-          if (lane == 0 && j0 + j < ns) {
-            es[(j0 + j) * Tp + tau] = r0;
-            if (tau1 < Tv) es[(j0 + j) * Tp + tau1] = r1;
-          }
-        }
-      }
-    }
-  }
-  __syncthreads();
-  if (virt && len + 1 < T) {
-    const int rest = T - len - 1;
-    for (int i = tid; i < ns * rest; i += NT) {
-      const int j = i / rest, tau = len + 1 + i - j * rest;
-      es[j * Tp + tau] = es[j * Tp + len];
-    }
-    __syncthreads();
-  }
-  // ---- 2. softmax over ALL T rows, mask finished rows, renormalise                   (:190-191)
-  for (int j = w; j < ns; j += NW) {
-    float* ej = es + j * Tp;
-    float m = -INFINITY;
-    for (int tau = lane; tau < T; tau += 64) m = fmaxf(m, ej[tau]);
-    m = wave_max(m);
-    float sm = 0.f;
-    for (int tau = lane; tau < T; tau += 64) sm += expf(ej[tau] - m);
-    sm = wave_sum(sm);
-    float s2 = 0.f;
-    for (int tau = lane; tau < T; tau += 64) {
-      float p = expf(ej[tau] - m) / sm;
-      p = tau < len ? p : 0.f;
-      ej[tau] = p;
-      s2 += p;
-    }
-    s2 = wave_sum(s2);
-    float* arow = a.atts + (size_t)j * T * N;
-    for (int tau = lane; tau < T; tau += 64) {
-      const float att = ej[tau] / s2;
-      ej[tau] = att;
-      arow[(size_t)tau * N + n] = att;
-    }
-  }
-  __syncthreads();
-  // ---- 3. ctx[j] = sum_tau att[j][tau] * eout[tau, n, :]  on the matrix cores          (:193)
-  // D[step][col] += A[step][k] B[k][col], k = encoder row: lane l holds A[l % 32][l / 32] (LDS) and
-  // B[l / 32][l % 32] (global); rows >= nsteps of A are zero, weights of rows >= len are zero
-  {
-    float* ctxS = eS;                                        // every wave is done with the eht rows
-    const int li = lane & 31, kh = lane >> 5;
-    const int nm = (len + 1) >> 1;                           // MFMAs (2 encoder rows each)
-    for (int cb = 32 * w; cb < L; cb += 32 * NW) {
-      f32x16 acc;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-      const float* bcol = a.eout + (size_t)n * L + cb + li;
-      for (int m0 = 0; m0 < nm; m0 += 8) {
-        float bv[8], av[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int tau = min(2 * (m0 + u) + kh, T - 1);
-          bv[u] = bcol[(size_t)tau * N * L];
-          av[u] = es[li * Tp + min(2 * (m0 + u) + kh, Tp - 1)];
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-          if (m0 + u < nm) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], bv[u], acc, 0, 0, 0);
-      }
-      // C/D layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int j = (r & 3) + 8 * (r >> 2) + 4 * kh;
-        if (j < ns) {
-          ctxS[(size_t)j * L + cb + li] = acc[r];
-          if (a.ctx_out) a.ctx_out[((size_t)j * N + n) * L + cb + li] = acc[r];
-        }
-      }
-    }
-  }
-  __syncthreads();
-  // ---- 4. token logits = [out, ctx] . W_y + b_y for all steps: one [32 x 2L] x [2L x 32] product on
-  // the matrix cores, K split over the 16 waves (a per-thread partial per (step, token) would cost 64
-  // wave reductions per wave and 4 steps -- as much VALU time as the tanh scores)       (:196-198)
-  {
-    const float* ctxS = eS;
-    float* part = eS + (size_t)nsteps * L;                   // [NW][nsteps][MAXV], behind the ctx rows
-    const int li = lane & 31, kh = lane >> 5;
-    const int kper = 2 * L / NW;                             // k range of this wave (64 at L = 512)
-    const int k0 = w * kper;
-    const int jr = min(li, ns - 1);
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    for (int m0 = 0; m0 < kper / 2; m0 += 8) {
-      float av[8], bv[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int k = k0 + 2 * (m0 + u) + kh;
-        av[u] = k < L ? a.out[((size_t)jr * N + n) * L + k] : ctxS[(size_t)jr * L + k - L];
-        bv[u] = li < V ? a.Wy[(size_t)k * V + li] : 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], bv[u], acc, 0, 0, 0);
-    }
-    if (li < MAXV) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int j = (r & 3) + 8 * (r >> 2) + 4 * kh;       // step (row of D), li = token (column)
-        if (j < ns) part[((size_t)w * nsteps + j) * MAXV + li] = acc[r];
-      }
-    }
-    __syncthreads();
-    for (int j = w; j < ns; j += NW) {
-      float sc = -INFINITY;
-      if (lane < V) {
-        sc = a.by[lane];
-        for (int ww = 0; ww < NW; ++ww) sc += part[((size_t)ww * nsteps + j) * MAXV + lane];
-      }
-      dec_token_tail(a, n, j, (size_t)j * N + n, sc, lane);
-    }
-  }
-}
-
-// dec_attn_ring_kernel: dec_attn_question_kernel resized to share a CU -- 8 waves, <= 48 KB of LDS -- so that
-// one of its workgroups fits beside a resident lstm_tile_kernel workgroup of the other stream (64 KB, 8
-// waves), or two of them beside each other.  Same arithmetic, same summation orders, bit-identical results:
-//   * the question's len + 1 encoder_h_transform rows are STREAMED through a two-slot ring of RING_ROWS-row
-//     chunks (2 x 16 KB) instead of resting in LDS: the next chunk is requested (LDS-DMA, no registers) before
+// dec_attn_ring_kernel: the teacher-forced attention of ONE question, ALL decoder steps, in one 8-wave
+// workgroup with <= 48 KB of LDS (nmn3_netgen_att.py:184-268 for every step at once), so that one of its
+// workgroups fits beside a resident lstm_tile_kernel workgroup of the other stream (64 KB, 8 waves), or two of
+// them beside each other.  dec_attn_multi_kernel gives a question to ceil(T_dec / 4) workgroups, each of which
+// streams the question's encoder rows again (PMC: 302 MB per 512-question launch for 94 MB of rows).  Here
+//   * the question's len + 1 encoder_h_transform rows are read from HBM/L2 ONCE, STREAMED through a two-slot
+//     ring of RING_ROWS-row chunks (2 x 16 KB): the next chunk is requested (LDS-DMA, no registers) before
 //     the tanh work of the current one and awaited behind it, one barrier per chunk;
-//   * 8 waves = 4 step groups of SPG steps x 2 row halves (few live steps: the idle waves go to the rows);
-//     the lane <-> k map (k = 4 lane + 256 i) and wave_sum of a score are those of the 16-wave kernel;
-//   * context: a wave owns 64 columns (two 32-column MFMA blocks that share the attention fragments), the
-//     order over encoder rows per column is unchanged;
-//   * token logits: the 16 K-slices of 2L / 16 stay, one accumulator each; wave w carries slices w (fed from
-//     global `out`) and w + 8 (fed from the context rows in LDS); the slices are added in order 0..15;
+//   * the tanh scores e[j][tau] = sum_k v_k tanh(q_j,k + eht[tau,k]) -- the VALU-bound part, two
+//     transcendentals per (step, row, k) -- are spread over the 8 waves as 4 step groups of SPG steps x 2 row
+//     halves: a wave keeps the query vectors of its 5 steps in registers (lane <-> k map k = 4 lane + 256 i)
+//     and walks its rows of the chunk in LDS; a question with few live steps (eos_retire) gives its idle
+//     waves to the rows instead;
+//   * the context vectors ctx[j] = sum_tau att[j][tau] eout[tau] are ONE small matrix product per question
+//     ([32 steps] x [len] x [L]) on the matrix cores (v_mfma_f32_32x32x2_f32): a wave owns 64 columns (two
+//     32-column MFMA blocks that share the attention fragments), its B fragments are the encoder_outputs rows
+//     straight from global memory, each element loaded exactly once, the attention weights come from LDS;
+//   * token logits: 16 K-slices of 2L / 16, one accumulator each; wave w carries slices w (fed from global
+//     `out`) and w + 8 (fed from the context rows in LDS); the slices are added in order 0..15; validity,
+//     probabilities and entropy as in the other attention kernels (dec_token_tail);
 //   * the ring space later holds the context rows [nsteps][L], then -- once the token-logit MFMAs have read
 //     them -- the [16][nsteps][MAXV] partial logits.
 constexpr int RING_ROWS = 8;
@@ -1188,12 +976,16 @@ __global__ __launch_bounds__(DEC_RING_THREADS, 5) void dec_attn_ring_kernel(DecS
   const int n = a.order ? a.order[blockIdx.x] : (int)blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int len = min(max(a.seq_len[n], 0), T);
-  // eos_retire: see dec_attn_question_kernel
+  // eos_retire (DecStepArgs::dec_len): only the steps that emit a module token are evaluated -- the steps
+  // from the first <eos> on feed nothing the caller asked for (decoder_impl); their tokens are the given
+  // ones.  `nsteps` keeps describing the launch (LDS layout, output strides), `ns` the work.
   const int ns = a.dec_len ? min(nsteps, max(a.dec_len[n], 0)) : nsteps;
   if (ns < nsteps) {
     for (int j = ns + tid; j < nsteps; j += NT) a.tokens[(size_t)j * N + n] = a.gt[(size_t)j * N + n];
     if (ns == 0) return;
   }
+  // rows past the question's length all equal the bias of encoder_h_transform: virtual row `len`
+  // stands for every one of them (evaluated once, copied to the others below)
   const bool virt = a.eht_bias && len < T;      // row `len` is the bias vector, not a row of eht
   const int Tv = virt ? len + 1 : T;
   const int nchunk = (Tv + RING_ROWS - 1) / RING_ROWS;
@@ -1238,8 +1030,8 @@ __global__ __launch_bounds__(DEC_RING_THREADS, 5) void dec_attn_ring_kernel(DecS
       const int tau_c = c * RING_ROWS;
       const int cn = min(RING_ROWS, Tv - tau_c);             // rows of this chunk
       if (j0 < ns) {
-        // one row per trip: the two-row trip of the 16-wave kernel costs 14 more VGPRs, which is the
-        // difference between 5 and 4 waves per SIMD here; a score is the same sum either way
+        // one row per trip: a two-row trip costs 14 more VGPRs, which is the difference between 5 and 4
+        // waves per SIMD here; a score is the same sum either way
         for (int r = tq; r < cn; r += nrq) {
           float4 e0[KI];
 #pragma unroll
@@ -1295,7 +1087,9 @@ __global__ __launch_bounds__(DEC_RING_THREADS, 5) void dec_attn_ring_kernel(DecS
   }
   __syncthreads();
   // ---- 3. ctx[j] = sum_tau att[j][tau] * eout[tau, n, :]  on the matrix cores          (:193)
-  // as in dec_attn_question_kernel; the two 32-column blocks of a wave share the A fragments
+  // D[step][col] += A[step][k] B[k][col], k = encoder row: lane l holds A[l % 32][l / 32] (LDS) and
+  // B[l / 32][l % 32] (global); rows >= nsteps of A are zero, weights of rows >= len are zero; the two
+  // 32-column blocks of a wave share the A fragments
   {
     float* ctxS = eS;                                        // every wave is done with the ring
     const int li = lane & 31, kh = lane >> 5;
@@ -1339,7 +1133,8 @@ __global__ __launch_bounds__(DEC_RING_THREADS, 5) void dec_attn_ring_kernel(DecS
   }
   __syncthreads();
   // ---- 4. token logits = [out, ctx] . W_y + b_y for all steps: one [32 x 2L] x [2L x 32] product on
-  // the matrix cores, K split into NSL slices, two per wave                              (:196-198)
+  // the matrix cores, K split into NSL slices, two per wave (a per-thread partial per (step, token) would
+  // cost 64 wave reductions per wave and 4 steps -- as much VALU time as the tanh scores)  (:196-198)
   {
     const float* ctxS = eS;
     float* part = eS;                                        // [NSL][nsteps][MAXV], over the ctx rows once read
@@ -1861,75 +1656,85 @@ static void launch_dec_multi(const DecStepArgs& a, int nsteps, hipStream_t s) {
 static size_t dec_ring_lds_bytes(int T, int L, int nsteps) {
   return sizeof(float) * ((size_t)dec_ring_floats(L, nsteps) + 32 * (size_t)((T + 3) & ~3));
 }
-// launches of the two per-question kernels in this process (n2nmn_debug_dec_attn: the A/B tests prove which ran)
-static std::atomic<uint64_t> g_dec_ring_launches{0}, g_dec_question_launches{0};
+// launches of dec_attn_ring_kernel in this process (n2nmn_debug_dec_attn: the tests prove that it ran)
+static std::atomic<uint64_t> g_dec_ring_launches{0};
 void dec_attn_debug(uint64_t out[4]) {
   out[0] = g_dec_ring_launches.load();
-  out[1] = g_dec_question_launches.load();
+  out[1] = 0;                                                // reserved
   out[2] = dec_ring_lds_bytes(45, 512, 20);
   out[3] = DEC_RING_THREADS;
 }
 
-template <int KI>
-static bool launch_dec_question(const DecStepArgs& a, int nsteps, hipStream_t s) {
-  const int Tp = (a.T + 3) & ~3;
-  const size_t smem = sizeof(float) * ((size_t)std::max(a.T, nsteps) * a.L + 32 * (size_t)Tp + 16 * 4 * MAXV);
-  if (smem > 150 * 1024 || (size_t)a.T * a.L > (size_t)3 * KI * 4096 ||
-      (size_t)nsteps * (a.L + 16 * MAXV) > (size_t)std::max(a.T, nsteps) * a.L) return false;
-  // the 8-wave ring form shares a CU with the other stream's workgroups (DecStepArgs::no_ring: the A/B switch)
-  const size_t ring = dec_ring_lds_bytes(a.T, a.L, nsteps);
-  if (!a.no_ring && a.L == 256 * KI && ring <= 48 * 1024 &&
-      (size_t)std::max(a.T, nsteps) * a.N * a.L < ((size_t)1 << 30)) {      // (32-bit lane offsets)
-    hipLaunchKernelGGL((dec_attn_ring_kernel<KI>), dim3(a.N), dim3(DEC_RING_THREADS), ring, s, a, nsteps);
-    ++g_dec_ring_launches;
-    return true;
+// Which kernel serves a decoder attention launch: the ONE statement of it (launch_dec_attn switches over it;
+// dec_len_supported / dec_seq_retire_supported answer decoder_impl from it).
+enum class DecAttnRoute {
+  Ring,      // dec_attn_ring_kernel<2>: one workgroup per question, all steps; honours dec_len
+  Multi,     // dec_attn_multi_kernel: 2 or 4 steps per workgroup (launch_dec_multi); honours dec_len
+  StepGrid,  // dec_attn_kernel<256> on a (question, step) grid
+  Seq,       // dec_attn_seq_kernel<2>: one sequential step, one pass
+  Generic    // dec_attn_kernel<1024>: one sequential step, three passes
+};
+static DecAttnRoute dec_attn_route(const DecStepArgs& a, int nsteps) {
+  if (nsteps <= 1) {
+    // one step per launch (greedy / sampled decoding): the one-pass form; the diagnostic build's
+    // N2NMN_DEC_ATTN_SEQ=0 keeps the three-pass kernel
+    static const bool seq_on = N2NMN_KNOB_INT("N2NMN_DEC_ATTN_SEQ", 1) != 0;
+    // (lstm_dim 1024 needs 128 VGPRs in the one-pass form: one workgroup per CU)
+    return seq_on && a.L == 512 ? DecAttnRoute::Seq : DecAttnRoute::Generic;
   }
-  static std::atomic<uint64_t> attr{0};
-  ensure_dynamic_lds(reinterpret_cast<const void*>(dec_attn_question_kernel<KI>), 150 * 1024, attr);
-  hipLaunchKernelGGL((dec_attn_question_kernel<KI>), dim3(a.N), dim3(1024), smem, s, a, nsteps);
-  ++g_dec_question_launches;
-  return true;
+  // every step of a question in one workgroup: needs a teacher-forced launch of <= 20 steps (4 groups of 5)
+  // and enough questions to fill the chip with one workgroup each.  The two conditions on T come from the
+  // LDS layout of the retired 16-wave kernel that kept all rows resident (T L <= 24 K floats of rows; the
+  // partial logits behind the context rows); the ring kernel needs neither, but widening them is a separate,
+  // measured change.  Together with nsteps <= 20 they bound the LDS request by 47 104 B.
+  static const int qk = N2NMN_KNOB_INT("N2NMN_DEC_ATTN_Q", 1);
+  const size_t rows = (size_t)std::max(a.T, nsteps);
+  if (qk && nsteps <= 20 && a.N >= 128 && !a.uni && !a.forced && a.use_gt && a.L == 512 &&
+      (size_t)a.T * a.L <= (size_t)3 * 2 * 4096 && (size_t)nsteps * (a.L + 16 * MAXV) <= rows * a.L &&
+      dec_ring_lds_bytes(a.T, a.L, nsteps) <= 48 * 1024 &&
+      rows * a.N * a.L < ((size_t)1 << 30))                  // (32-bit lane offsets)
+    return DecAttnRoute::Ring;
+  return a.L % 256 == 0 && a.L <= 1024 ? DecAttnRoute::Multi : DecAttnRoute::StepGrid;
 }
 
 void launch_dec_attn(const DecStepArgs& a, int nsteps, hipStream_t s) {
-  // every step of a question in one workgroup: needs <= 20 steps (4 groups of 5), enough questions to
-  // fill the chip with one workgroup each, and the question's rows in LDS
-  static const int qk = N2NMN_KNOB_INT("N2NMN_DEC_ATTN_Q", 1);
-  if (qk && nsteps > 1 && nsteps <= 20 && a.N >= 128 && !a.uni && !a.forced && a.use_gt) {
-    if (a.L == 512 && launch_dec_question<2>(a, nsteps, s)) return;
-  }
-  if (nsteps > 1 && a.L % 256 == 0 && a.L <= 1024) {
-    // steps per workgroup: as many as keep >= ~2 workgroups per CU in the launch
-    const int groups4 = (nsteps + 3) / 4;
-    const bool four = (long)a.N * groups4 >= 512 || nsteps <= 2;
-    if (a.L <= 512) {
-      if (four) launch_dec_multi<2, 4>(a, nsteps, s);
-      else launch_dec_multi<2, 2>(a, nsteps, s);
-    } else {
-      if (four) launch_dec_multi<4, 4>(a, nsteps, s);
-      else launch_dec_multi<4, 2>(a, nsteps, s);
+  // LDS of dec_attn_kernel<NT>
+  auto step_lds = [&](int nt) {
+    const int nsplit = std::min(8, std::max(1, nt / (a.L / 4)));
+    return sizeof(float) * ((2 + (size_t)nsplit) * a.L + ((a.T + 3) & ~3) + (size_t)(nt / 64) * MAXV + 16);
+  };
+  switch (dec_attn_route(a, nsteps)) {
+    case DecAttnRoute::Ring:
+      // shares a CU with the other stream's workgroups
+      hipLaunchKernelGGL((dec_attn_ring_kernel<2>), dim3(a.N), dim3(DEC_RING_THREADS),
+                         dec_ring_lds_bytes(a.T, a.L, nsteps), s, a, nsteps);
+      ++g_dec_ring_launches;
+      return;
+    case DecAttnRoute::Multi: {
+      // steps per workgroup: as many as keep >= ~2 workgroups per CU in the launch
+      const int groups4 = (nsteps + 3) / 4;
+      const bool four = (long)a.N * groups4 >= 512 || nsteps <= 2;
+      if (a.L <= 512) {
+        if (four) launch_dec_multi<2, 4>(a, nsteps, s);
+        else launch_dec_multi<2, 2>(a, nsteps, s);
+      } else {
+        if (four) launch_dec_multi<4, 4>(a, nsteps, s);
+        else launch_dec_multi<4, 2>(a, nsteps, s);
+      }
+      return;
     }
-    return;
+    case DecAttnRoute::StepGrid:
+      hipLaunchKernelGGL(dec_attn_kernel<256>, dim3(a.N, nsteps), dim3(256), step_lds(256), s, a);
+      return;
+    case DecAttnRoute::Seq: {
+      const size_t sm = sizeof(float) * ((2 + 16) * (size_t)a.L + ((a.T + 3) & ~3) + 4 * 16 + 16 * MAXV + 16);
+      hipLaunchKernelGGL(dec_attn_seq_kernel<2>, dim3(a.N), dim3(1024), sm, s, a);
+      return;
+    }
+    case DecAttnRoute::Generic:
+      hipLaunchKernelGGL(dec_attn_kernel<1024>, dim3(a.N, 1), dim3(1024), step_lds(1024), s, a);
+      return;
   }
-  const int nt = nsteps > 1 ? 256 : 1024;
-  const int ncol = a.L / 4;
-  int nsplit = nt / ncol;
-  nsplit = nsplit < 1 ? 1 : (nsplit > 8 ? 8 : nsplit);
-  const size_t smem = sizeof(float) * ((2 + (size_t)nsplit) * a.L + ((a.T + 3) & ~3) +
-                                       (size_t)(nt / 64) * MAXV + 16);
-  if (nsteps > 1) {
-    hipLaunchKernelGGL(dec_attn_kernel<256>, dim3(a.N, nsteps), dim3(256), smem, s, a);
-    return;
-  }
-  // one step per launch (greedy / sampled decoding): the one-pass form; the diagnostic build's N2NMN_DEC_ATTN_SEQ=0 keeps the
-  // three-pass kernel
-  static const bool seq_on = N2NMN_KNOB_INT("N2NMN_DEC_ATTN_SEQ", 1) != 0;
-  if (seq_on && a.L == 512) {       // (lstm_dim 1024 needs 128 VGPRs in this form: one workgroup per CU)
-    const size_t sm = sizeof(float) * ((2 + 16) * (size_t)a.L + ((a.T + 3) & ~3) + 4 * 16 + 16 * MAXV + 16);
-    hipLaunchKernelGGL(dec_attn_seq_kernel<2>, dim3(a.N), dim3(1024), sm, s, a);
-    return;
-  }
-  hipLaunchKernelGGL(dec_attn_kernel<1024>, dim3(a.N, 1), dim3(1024), smem, s, a);
 }
 
 void launch_enc_rows(const int32_t* seq_len, int T, int N, int32_t* rows, int32_t* count,
@@ -1955,9 +1760,9 @@ void launch_enc_prepare(const int32_t* seq_len, int N, int T, int32_t* perm, int
                      reinterpret_cast<float4*>(zero), zero ? z4 : 0, zero_int);
 }
 
-bool dec_seq_retire_supported(const DecStepArgs& a) {     // the one-step launches go to dec_attn_seq_kernel
-  static const bool seq_on = N2NMN_KNOB_INT("N2NMN_DEC_ATTN_SEQ", 1) != 0;
-  return seq_on && a.L == 512 && a.N <= 1024;
+// sequential eos_retire: the one-step launches must go to dec_attn_seq_kernel (live_perm / live_n)
+bool dec_seq_retire_supported(const DecStepArgs& a) {
+  return dec_attn_route(a, 1) == DecAttnRoute::Seq && a.N <= 1024;
 }
 
 void launch_dec_compact(const int32_t* tokens, const int32_t* token_op, int V, const int32_t* perm_old,
@@ -1988,19 +1793,11 @@ void launch_gather_state(const float* const src[4], float* const dst[4], const u
   hipLaunchKernelGGL(gather_state_kernel, dim3((N + 63) / 64, std::min(32, std::max(1, L / 16))), dim3(256), 0, s, g);
 }
 
-// teacher-forced launches whose attention kernel honours DecStepArgs::dec_len: dec_attn_question_kernel
-// (lstm_dim 512) or dec_attn_multi_kernel (launch_dec_attn's choice for every other lstm_dim % 256 == 0)
+// teacher-forced launches whose attention kernel honours DecStepArgs::dec_len: dec_attn_ring_kernel or
+// dec_attn_multi_kernel
 bool dec_len_supported(const DecStepArgs& a, int nsteps) {
-  return dec_question_supported(a, nsteps) ||
-         (nsteps > 1 && a.L % 256 == 0 && a.L <= 1024 && !a.uni && !a.forced && a.use_gt);
-}
-
-bool dec_question_supported(const DecStepArgs& a, int nsteps) {
-  const int Tp = (a.T + 3) & ~3;
-  const size_t smem = sizeof(float) * ((size_t)std::max(a.T, nsteps) * a.L + 32 * (size_t)Tp + 16 * 4 * MAXV);
-  return nsteps > 1 && nsteps <= 20 && a.N >= 128 && !a.uni && !a.forced && a.use_gt && a.L == 512 &&
-         !(smem > 150 * 1024 || (size_t)a.T * a.L > (size_t)3 * 2 * 4096 ||
-           (size_t)nsteps * (a.L + 16 * MAXV) > (size_t)std::max(a.T, nsteps) * a.L);
+  const DecAttnRoute r = dec_attn_route(a, nsteps);
+  return (r == DecAttnRoute::Ring || r == DecAttnRoute::Multi) && !a.uni && !a.forced && a.use_gt;
 }
 
 void launch_dec_init(int32_t* state, int N, int T_dec, hipStream_t s) {

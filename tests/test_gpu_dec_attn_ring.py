@@ -1,11 +1,11 @@
 """dec_attn_ring_kernel (csrc/kernels_seq2seq.hip): the teacher-forced decoder attention of one question in an
 8-wave workgroup with at most 48 KB of LDS, the question's encoder_h_transform rows streamed through a two-slot
-ring of 8-row chunks -- against dec_attn_question_kernel (16 waves, 100 KB, all rows resident), which
-n2nmn_debug_set "dec_attn_ring" = 0 keeps selecting.  Both kernels add every sum in the same order, so every
-output of the decoder must be the SAME BITS under both settings, and both must meet the fp64 oracle at the
-tolerances of test_gpu_seq2seq.py (util.check_decoder).
+ring of 8-row chunks by LDS-DMA.  Every case runs twice on the same context: the launch counter of
+n2nmn_debug_dec_attn proves that each run went through the ring kernel, the two runs must return the SAME BITS in
+every fetched output (a missed wait in the ring shows as a run that scored rows still in flight), and the outputs
+must meet the fp64 oracle at the tolerances of test_gpu_seq2seq.py (util.check_decoder).
 
-Shapes: N = 128 (the smallest launch that reaches these kernels), lstm_dim 512, T_enc 45; question lengths 1,
+Shapes: N = 128 (the smallest launch that reaches the kernel), lstm_dim 512, T_enc 45; question lengths 1,
 chunk - 1, chunk, chunk + 1, 2 chunk, 44 and 45 (45: no virtual bias row) plus a seeded random remainder; T_dec 2,
 5, 6, 11, 20 (one, two and four step groups of five, full and partly filled); layouts that end after 0, 1, 5, 6
 and all steps under eos_retire; and two contexts on two streams at once, one of them with 1024-row encoder steps."""
@@ -66,40 +66,32 @@ def _layouts(Td, seed, lengths=None):
 
 
 def _launches(eng):
-    """launches of (dec_attn_ring_kernel, dec_attn_question_kernel) in this process so far"""
+    """launches of dec_attn_ring_kernel in this process so far (slot 0 of n2nmn_debug_dec_attn)"""
     out = (ctypes.c_uint64 * 4)()
     _lib.check(eng._lib.n2nmn_debug_dec_attn(eng._ctx, out))
-    return int(out[0]), int(out[1])
-
-
-def _both(eng, run):
-    """run() under dec_attn_ring = 1 and = 0 on the same context; the launch counters prove that the first ran
-    the ring kernel only and the second the resident kernel only (two settings that reached the same kernel
-    would agree bit for bit too)"""
-    got = []
-    try:
-        for ring in (1, 0):
-            eng.debug_set('dec_attn_ring', ring)
-            before = _launches(eng)
-            got.append(run())
-            after = _launches(eng)
-            new = (after[0] - before[0], after[1] - before[1])
-            used = 0 if ring else 1
-            assert new[used] >= 1 and new[1 - used] == 0, \
-                'dec_attn_ring = %d launched (ring, resident) = %s' % (ring, new)
-    finally:
-        eng.debug_set('dec_attn_ring', None)
-    return got
+    return int(out[0])
 
 
 def _same_bits(what, a, b):
     for k in a:
-        assert np.array_equal(a[k], b[k]), '%s: %s differs between dec_attn_ring = 1 and 0 (max |diff| %.3e)' % (
+        assert np.array_equal(a[k], b[k]), '%s: %s differs between two runs (max |diff| %.3e)' % (
             what, k, float(np.max(np.abs(a[k].astype(np.float64) - b[k].astype(np.float64)))))
 
 
+def _twice(what, eng, run):
+    """run() twice on the same context: each run launched the ring kernel at least once, and the two returned the
+    same bits in every fetched output; the first run's outputs"""
+    got = []
+    for i in range(2):
+        before = _launches(eng)
+        got.append(run())
+        assert _launches(eng) - before >= 1, '%s: run %d did not launch dec_attn_ring_kernel' % (what, i)
+    _same_bits(what, got[0], got[1])
+    return got[0]
+
+
 @pytest.mark.parametrize('Td', [2, 5, 6, 11, 20])
-def test_ring_kernel_equals_the_resident_kernel_bit_for_bit(big, questions, Td):
+def test_ring_kernel_meets_the_oracle_and_repeats_bit_for_bit(big, questions, Td):
     eng, d, asm, w = big
     batch, enc = questions
     gt, _ = _layouts(Td, seed=Td)
@@ -110,8 +102,7 @@ def test_ring_kernel_equals_the_resident_kernel_bit_for_bit(big, questions, Td):
         torch.cuda.synchronize()
         return {k: t2n(out[k]).copy() for k in FETCH}
 
-    ring, resident = _both(eng, run)
-    _same_bits('T_dec %d' % Td, ring, resident)
+    ring = _twice('T_dec %d' % Td, eng, run)
     assert np.array_equal(ring['predicted_tokens'], gt)
     dec = O.decoder_forward(w, enc, asm.P, asm.W, asm.b, Td, np.float64, use_gt_layout=True, gt_layout=gt)
     diffs = check_decoder(ring, dec)
@@ -124,27 +115,31 @@ def test_ring_kernel_equals_the_resident_kernel_bit_for_bit(big, questions, Td):
     assert np.abs(ring['atts'].sum(axis=1) - 1.0).max() < 1e-5
 
 
-def test_unknown_setting_is_refused_and_the_key_is_known(big):
+def test_unknown_setting_is_refused_and_the_retired_key_with_it(big):
     eng = big[0]
-    eng.debug_set('dec_attn_ring', 0)
-    eng.debug_set('dec_attn_ring', None)
-    with pytest.raises(KeyError):
-        eng.debug_set('dec_attn_rings', 1)
+    for key in ('dec_attn_ring', 'dec_attn_rings'):
+        with pytest.raises(KeyError):
+            eng.debug_set(key, 1)
 
 
 def test_logits_tokens_and_validity_of_a_whole_pass(big, questions):
-    """decoder -> layout walker: scores, tokens and validity of Engine.forward under both settings"""
+    """decoder -> layout walker: scores, tokens and validity of Engine.forward, scores against the fp64 oracle"""
     eng, d, asm, w = big
-    batch, _ = questions
+    batch, enc = questions
     gt = synth.template_layout_batch(d, n=N, offset=3)
 
     def run():
         sc, tok, val = eng.forward(batch, use_gt_layout=True, gt_layout=gt)
         return dict(scores=t2n(sc).copy(), tokens=np.asarray(tok).copy(), validity=np.asarray(val).copy())
 
-    ring, resident = _both(eng, run)
-    _same_bits('forward', ring, resident)
+    ring = _twice('forward', eng, run)
     assert np.array_equal(ring['tokens'], gt) and ring['validity'].all()
+    # O.forward's stages on the shared fp64 encoder; bar and helper of test_gpu_end2end.py
+    dec = O.decoder_forward(w, enc, asm.P, asm.W, asm.b, d.T_decoder, np.float64, use_gt_layout=True, gt_layout=gt)
+    exprs, validity = O.assemble(NAMES, dec['predicted_tokens'])
+    assert validity.all()
+    ref = O.execute_layouts(w, exprs, batch['image_feat_batch'], dec['word_vecs'], d.num_choices, np.float64)
+    assert_close('scores', ring['scores'], ref, 1e-4)
 
 
 def test_layouts_that_end_early_under_eos_retire(big, questions):
@@ -169,10 +164,9 @@ def test_layouts_that_end_early_under_eos_retire(big, questions):
 
     eng.set_mode('throughput')
     try:
-        ring, resident = _both(eng, run)
+        ring = _twice('eos_retire', eng, run)
     finally:
         eng.set_mode('latency')
-    _same_bits('eos_retire', ring, resident)
     assert np.array_equal(ring['predicted_tokens'], gt)
     live = np.arange(Td)[:, None] < k[None, :]                          # [Td, N]
     dead_att = ring['atts'][np.broadcast_to(~live[:, None, :], ring['atts'].shape)]
@@ -186,7 +180,7 @@ def test_layouts_that_end_early_under_eos_retire(big, questions):
 
 def test_context_vectors_of_a_training_forward(questions):
     """the context vectors only the backward pass reads (n2nmn_train_debug_tensor "dec_ctx") and the recorded
-    token logits: same bits under both settings, and ctx = sum_tau att[tau] encoder_outputs[tau] of the oracle"""
+    token logits: same bits in two runs, and ctx = sum_tau att[tau] encoder_outputs[tau] of the oracle"""
     from n2nmn_amd.nmn3_assembler import Assembler
     from n2nmn_amd.engine import Engine
     from n2nmn_amd.train import Trainer
@@ -207,8 +201,7 @@ def test_context_vectors_of_a_training_forward(questions):
         torch.cuda.synchronize()
         return out
 
-    ring, resident = _both(eng, run)
-    _same_bits('training forward', ring, resident)
+    ring = _twice('training forward', eng, run)
     dec = O.decoder_forward(w, enc, asm.P, asm.W, asm.b, Td, np.float64, use_gt_layout=True, gt_layout=gt)
     ctx = np.einsum('jtn,tnl->jnl', dec['atts'][..., 0], enc['outputs'])
     assert_close('dec_ctx', ring['dec_ctx'], ctx, 1e-4)
