@@ -881,6 +881,34 @@ int n2nmn_resnet_debug_conv1x1(const float *in, const float *w, const float *bia
                                float *out, int N, int H, int W, int Cin, int Cout, int stride, int relu,
                                n2nmn_stream stream);
 
+/* ------------------------------------------------------------------------------------------
+ * (11) compact feature feed: image features are the outputs of a frozen extractor, so they may be stored and
+ *     shipped as IEEE halves, and one row per IMAGE serves every question of a batch that asks about it (the
+ *     readers of util/clevr_train/data_reader.py:58 and util/vqa_train/data_reader.py:97 np.load the same
+ *     feature_path once per question).  Both reduce to  slot[n] = widen(src[index[n]])  behind a smaller H2D
+ *     copy; every entry point above keeps reading the fp32 [N][H][W][D] grid.  No handle, no state: both entries
+ *     run on the current device (like n2nmn_vgg_debug_conv) and are asynchronous on `stream`.
+ *     csrc/kernels_feed.hip, DESIGN.md section 14.
+ * ---------------------------------------------------------------------------------------- */
+#define N2NMN_FEAT_F32 0
+#define N2NMN_FEAT_F16 1
+/* dst[n][p][0:D] = (float) src[index ? index[n] : n][p][0:D],  n < N, p < pixels.
+ * src: device, dense [src_rows][pixels][D] of src_dtype.  index: device int32 [N] or NULL (then N <= src_rows).
+ * dst: device fp32 [N][pixels][dst_pixel_stride], dst_pixel_stride >= D; elements D .. stride-1 of a pixel are
+ * NOT written (the models_vqa slab keeps its coordinate channels and padding there).
+ * Widening is exact (subnormals, signed zeros, infinities; NaN stays NaN).  Any alignment of whole elements is
+ * accepted: 16-byte accesses when D % 8 == 0 (fp16 source) or D % 4 == 0 (fp32 source), the stride is a multiple
+ * of 4 and both pointers are 16-byte aligned, else one element per lane.
+ * An index outside [0, src_rows) makes that row zeros; nothing outside src is ever read.
+ * N == 0: success, no launch.  N2NMN_EINVAL: null pointers with non-zero sizes, negative sizes,
+ * dst_pixel_stride < D, an unknown dtype; N2NMN_ECAPACITY: a row of 2^31 elements or more.
+ * src and dst must not overlap. */
+int n2nmn_features_expand(const void *src, int src_dtype, int64_t src_rows, const int32_t *index, int64_t N,
+                          int64_t pixels, int64_t D, int64_t dst_pixel_stride, float *dst, n2nmn_stream stream);
+/* dst[i] = half(src[i]) round-to-nearest-even, overflow to infinity, subnormal results kept; i < n; any
+ * alignment of whole elements.  n == 0: success, no launch.  N2NMN_EINVAL: null pointers with n > 0, n < 0. */
+int n2nmn_features_narrow(const float *src, int64_t n, void *dst_f16, n2nmn_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

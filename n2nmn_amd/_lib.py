@@ -182,6 +182,9 @@ SYMBOLS = [
     ('n2nmn_resnet_debug_stem', _I, [_P, _I, _P, _P, C.POINTER(C.c_float), _P, _I, _I, _I, _I, _P]),
     ('n2nmn_resnet_debug_pool', _I, [_P, _P, _I, _I, _I, _I, _P]),
     ('n2nmn_resnet_debug_conv1x1', _I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    # section 11: the compact feature feed (no handle)
+    ('n2nmn_features_expand', _I, [_P, _I, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, _P]),
+    ('n2nmn_features_narrow', _I, [_P, C.c_int64, _P, _P]),
 ]
 
 

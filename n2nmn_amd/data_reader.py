@@ -20,6 +20,13 @@ Device half (MI355X): `DeviceFeeder` moves each batch through pinned host stagin
 `SuperBucket` on a copy stream of its own, so the H2D copy of batch i+1 (19.7 MB of CLEVR features
 = 0.3 ms on PCIe Gen5) runs under the compute of batch i; the consumer orders its stream after the
 slot's copy event and never blocks the host.
+
+Compact feed (opt-in; without the options a batch is what the reference's is, key for key and bit for
+bit): `feature_dtype='float16'` keeps the features in IEEE half from the file to the device, and
+`dedupe_features=True` delivers ONE feature row per distinct `feature_path` of a batch plus an
+`image_index_batch` (CLEVR asks about ten questions per image, VQA about five, and in dataset order they
+are neighbours).  The feeder then copies only those rows and the index, and n2nmn_features_expand
+(include/n2nmn.h section 11) widens / gathers them into the slot on the copy stream, behind the copy.
 """
 from __future__ import annotations
 
@@ -29,6 +36,8 @@ import threading
 from typing import Dict, Iterable, Iterator, List, Optional
 
 import numpy as np
+
+from .feed import expand, half_requested
 
 _SPLIT = re.compile(r'(\W+)')
 
@@ -87,6 +96,10 @@ class _Loader:
         self.load_answer = first.get(self.answer_key) is not None
         self.load_gt_layout = data_params.get('load_gt_layout', first.get('gt_layout_tokens') is not None)
         self.feat_H, self.feat_W, self.feat_D = np.load(first['feature_path']).shape[1:]
+        # the compact feed (module docstring): container precision of image_feat_batch, one row per image
+        self.feature_dtype = np.dtype(np.float16 if half_requested(data_params.get('feature_dtype'))
+                                      else np.float32)
+        self.dedupe_features = bool(data_params.get('dedupe_features', False))
 
     # hooks ------------------------------------------------------------------------------------
     def _layout_tokens(self, iminfo) -> List[str]:
@@ -100,14 +113,24 @@ class _Loader:
 
     def load_one_batch(self, sample_ids, out: Optional[Dict[str, np.ndarray]] = None):
         """out (optional): preallocated arrays (e.g. pinned) for input_seq_batch / seq_length_batch /
-        image_feat_batch (/ answer_label_batch / gt_layout_batch) of at least this batch size; the
-        returned batch then holds views of them."""
+        image_feat_batch (/ answer_label_batch / gt_layout_batch / image_index_batch) of at least this
+        batch size; the returned batch then holds views of them.
+
+        image_feat_batch is float32, or float16 with feature_dtype='float16' (fp16 files as they are, fp32
+        files rounded to nearest even by numpy).  With dedupe_features it holds one row per distinct
+        feature_path of the batch, in order of first occurrence ([U, H, W, D]; np.load runs once per path),
+        and image_index_batch (int32 [nb]) names each question's row."""
         nb = len(sample_ids)
+        row_of = None
+        if self.dedupe_features:
+            first_row = {}
+            row_of = [first_row.setdefault(self.imdb[sid]['feature_path'], len(first_row)) for sid in sample_ids]
+        nfeat = nb if row_of is None else len(first_row)
 
         def arr(key, shape, dtype):
             if out is not None and key in out:
                 a = out[key]
-                a = a[..., :nb] if key in ('input_seq_batch', 'gt_layout_batch') else a[:nb]
+                a = a[..., :nb] if key in ('input_seq_batch', 'gt_layout_batch') else a[:shape[0]]
                 if key != 'image_feat_batch':    # (every image row is overwritten below)
                     a[...] = 0
                 return a
@@ -116,20 +139,28 @@ class _Loader:
         batch = dict(
             input_seq_batch=arr('input_seq_batch', (self.T_encoder, nb), np.int32),
             seq_length_batch=arr('seq_length_batch', (nb,), np.int32),
-            image_feat_batch=arr('image_feat_batch', (nb, self.feat_H, self.feat_W, self.feat_D),
-                                 np.float32),
+            image_feat_batch=arr('image_feat_batch', (nfeat, self.feat_H, self.feat_W, self.feat_D),
+                                 self.feature_dtype),
             image_path_list=[None] * nb)
+        if row_of is not None:
+            batch['image_index_batch'] = arr('image_index_batch', (nb,), np.int32)
+            batch['image_index_batch'][:] = row_of
         if self.load_answer:
             batch['answer_label_batch'] = arr('answer_label_batch', (nb,), np.int32)
         if self.load_gt_layout:
             batch['gt_layout_batch'] = arr('gt_layout_batch', (self.T_decoder, nb), np.int32)
         self._begin(batch, nb)
+        n_loaded = 0
         for n, sid in enumerate(sample_ids):
             iminfo = self.imdb[sid]
             inds = [self.vocab_dict.word2idx(w) for w in iminfo['question_tokens']]
             batch['input_seq_batch'][:len(inds), n] = inds
             batch['seq_length_batch'][n] = len(inds)
-            batch['image_feat_batch'][n:n + 1] = np.load(iminfo['feature_path'])
+            if row_of is None:
+                batch['image_feat_batch'][n:n + 1] = np.load(iminfo['feature_path'])
+            elif row_of[n] == n_loaded:          # the first question about this image
+                batch['image_feat_batch'][n_loaded:n_loaded + 1] = np.load(iminfo['feature_path'])
+                n_loaded += 1
             batch['image_path_list'][n] = iminfo['image_path']
             self._extra(batch, n, iminfo)
             if self.load_gt_layout:
@@ -349,13 +380,24 @@ class DeviceFeeder:
         def pinned(shape, dtype):
             return torch.empty(shape, dtype=dtype).pin_memory()
 
+        # the compact feed: staging in the reader's container dtype, and per slot a device landing buffer of
+        # that dtype plus an index buffer; the expand into the slot runs on the copy stream behind the copies
+        # (one stream: the landing buffer needs no event of its own)
+        half = bl.feature_dtype == np.float16
+        self.dedupe = bool(bl.dedupe_features)
+        self.compact = half or self.dedupe
+        feat_dtype = torch.float16 if half else torch.float32
+        feat_shape = (Nb, bl.feat_H, bl.feat_W, bl.feat_D)
+
         def staging_set():
             t = dict(input_seq_batch=pinned((d.T_encoder, Nb), torch.int32),
                      seq_length_batch=pinned((Nb,), torch.int32),
-                     image_feat_batch=pinned((Nb, bl.feat_H, bl.feat_W, bl.feat_D), torch.float32),
+                     image_feat_batch=pinned(feat_shape, feat_dtype),
                      gt_layout_batch=pinned((d.T_decoder, Nb), torch.int32))
             if not (use_gt_layout and getattr(bl, 'load_gt_layout', False)):
                 del t['gt_layout_batch']
+            if self.dedupe:
+                t['image_index_batch'] = pinned((Nb,), torch.int32)
             st = {k: v.numpy() for k, v in t.items()}     # numpy views of the pinned storage
             st['_pinned'] = t
             return st
@@ -372,16 +414,30 @@ class DeviceFeeder:
         self.copied = [torch.cuda.Event() for _ in self.buckets]    # staging sets free again
         self.released = [torch.cuda.Event() for _ in self.buckets]  # bucket free again
         self._used = [False] * len(self.buckets)
+        self.landing = self.index_dev = None
+        if self.compact:
+            self.landing = [[torch.empty(feat_shape, dtype=feat_dtype, device=self.device) for _ in range(K)]
+                            for _ in self.buckets]
+            self.index_dev = [[torch.empty((Nb,), dtype=torch.int32, device=self.device) for _ in range(K)]
+                              for _ in self.buckets]
 
     @staticmethod
     def _rows(t, key, nb):
         return t[..., :nb] if key in ('input_seq_batch', 'gt_layout_batch') else t[:nb]
 
+    def _dest(self, s, k, slot, key):
+        """where the H2D copy of `key` lands: the slot itself, or for a compact feed the landing / index buffer"""
+        if key == 'image_feat_batch' and self.compact:
+            return self.landing[s][k]
+        if key == 'image_index_batch':
+            return self.index_dev[s][k]
+        return slot[key]
+
     def groups(self):
         torch = self.torch
         it = self.reader.batches()
         keys = ('input_seq_batch', 'seq_length_batch', 'image_feat_batch') + \
-            (('gt_layout_batch',) if self.use_gt else ())
+            (('gt_layout_batch',) if self.use_gt else ()) + (('image_index_batch',) if self.dedupe else ())
         g = 0
         while True:
             s = g % len(self.buckets)
@@ -399,6 +455,9 @@ class DeviceFeeder:
                     if b is None:
                         break
                     nb = b['seq_length_batch'].shape[0]
+                    # (feature rows: nb, or with dedupe_features the U <= nb distinct images of the batch)
+                    nfeat = b['image_feat_batch'].shape[0]
+                    rows_of = {key: nfeat if key == 'image_feat_batch' else nb for key in keys}.get
                     slot = bucket.slot(k)
                     st = b.pop('_staging', None)
                     if st is not None:
@@ -408,11 +467,15 @@ class DeviceFeeder:
                             self.stage[s][k] = self._staging_set()
                         st = self.stage[s][k]
                         for key in keys:
-                            self._rows(st['_pinned'][key], key, nb).copy_(
+                            self._rows(st['_pinned'][key], key, rows_of(key)).copy_(
                                 torch.from_numpy(np.ascontiguousarray(b[key])))
                     for key in keys:
-                        src = self._rows(st['_pinned'][key], key, nb)
-                        self._rows(slot[key], key, nb).copy_(src, non_blocking=True)
+                        rows = rows_of(key)
+                        src = self._rows(st['_pinned'][key], key, rows)
+                        self._rows(self._dest(s, k, slot, key), key, rows).copy_(src, non_blocking=True)
+                    if self.compact:
+                        expand(self.landing[s][k][:nfeat], self.index_dev[s][k][:nb] if self.dedupe else None,
+                               slot['image_feat_batch'][:nb])
                     if nb < bucket.Nb:           # short last batch: the rest of the slot is padding
                         slot['seq_length_batch'][nb:].fill_(1)
                     # Lifetime of what the consumer sees in group.batches: a batch built inside a
@@ -421,7 +484,7 @@ class DeviceFeeder:
                     # (tokens, lengths, layouts: a few KB) are therefore copied out here, so a consumer
                     # may keep them for logging or accumulation; only the 20 MB `image_feat_batch`
                     # stays an alias, valid until the group after next is requested.
-                    for key in ('input_seq_batch', 'seq_length_batch', 'gt_layout_batch'):
+                    for key in ('input_seq_batch', 'seq_length_batch', 'gt_layout_batch', 'image_index_batch'):
                         if key in b and isinstance(b[key], np.ndarray) and not b[key].flags.owndata:
                             b[key] = np.array(b[key])
                     batches.append(b)

@@ -11,7 +11,7 @@ from typing import Dict, Optional
 
 import numpy as np
 
-from . import _lib
+from . import _lib, feed
 from .nmn3_assembler import Assembler, PackedLayouts
 from .spec import Dims, OP_CODE, MODULE_INPUT_NUM, MODULE_OUTPUT_TYPE
 
@@ -171,6 +171,48 @@ class Engine:
         if t.device != self.device or t.dtype != dtype or not t.is_contiguous():
             t = t.to(device=self.device, dtype=dtype).contiguous()
         return t
+
+    def features(self, image_feat, index=None, n: Optional[int] = None):
+        """The dense float32 device grid [N, H, W, D] the kernels read, from what a reader delivers.
+        float32 features without an index: exactly `_dev(image_feat, float32)`, nothing else runs.  float16
+        features and / or `index` (int32 [N] into the rows of image_feat: one row per IMAGE, shared by the
+        questions about it): the features cross the link as they are and n2nmn_features_expand widens /
+        gathers them on the current stream -- out[i] = float(image_feat[index[i]]), exact.  An index held on
+        the host is checked before any device call: a value outside [0, rows), or a length other than `n`
+        when n is given, is a ValueError."""
+        if index is None and not feed.is_half(image_feat):
+            return self._dev(image_feat, _torch().float32)
+        src, index, N = self.feature_source(image_feat, index, n)
+        out = _torch().empty((N,) + tuple(src.shape[1:]), dtype=_torch().float32, device=self.device)
+        return feed.expand(src, index, out)
+
+    def feature_source(self, image_feat, index=None, n: Optional[int] = None):
+        """What n2nmn_features_expand reads, for features() and the faces that expand into a buffer of their own
+        (SuperBucket.fill, VQAEngine.fill_slab): (the feature rows on the device in their own container -- float16
+        stays float16 --, the index on the device or None, the number of rows the expand writes).  The checks of
+        features() come first; nothing touches the device before they pass."""
+        if not hasattr(image_feat, 'shape'):
+            image_feat = np.asarray(image_feat)
+        rows = int(image_feat.shape[0])
+        if index is not None:
+            index = feed.check_index(index, rows, n)
+        elif n is not None and rows != n:
+            raise ValueError('%d feature rows for %d questions need an image index' % (rows, n))
+        torch = _torch()
+        src = torch.as_tensor(image_feat)
+        if src.dtype != torch.float16:
+            src = src.to(torch.float32)
+        src = src.to(device=self.device, non_blocking=True).contiguous()
+        if isinstance(index, np.ndarray):
+            index = self.upload_i32(index)
+        return src, index, rows if index is None else int(index.shape[0])
+
+    def _batch_features(self, batch):
+        """features() of a reader batch: `image_feat_batch` (+ `image_index_batch`, one entry per question)"""
+        index = batch.get('image_index_batch')
+        if index is None and not feed.is_half(batch['image_feat_batch']):
+            return self._dev(batch['image_feat_batch'], _torch().float32)
+        return self.features(batch['image_feat_batch'], index, n=int(batch['seq_length_batch'].shape[0]))
 
     def upload_i32(self, host):
         """Host int32 array -> device through a pinned slot, WITHOUT synchronising the stream (a
@@ -603,7 +645,7 @@ class Engine:
             torch = _torch()
             gt_dev = self.upload_i32(gt_layout) if isinstance(gt_layout, np.ndarray) else \
                 self._dev(gt_layout, torch.int32)
-            feat = self._dev(batch['image_feat_batch'], torch.float32)
+            feat = self._batch_features(batch)
             cur = torch.cuda.current_stream(self.device)
             if self._side is None:
                 self._side = torch.cuda.Stream(device=self.device)
@@ -654,6 +696,8 @@ class Engine:
             return scores, s2s['predicted_tokens'].cpu().numpy(), validity.cpu().numpy().astype(bool)
         if out is not None:
             raise ValueError('out= needs the device path (walker dimensions, host_assemble=False)')
+        if feed.is_compact(batch):
+            batch = dict(batch, image_feat_batch=self._batch_features(batch))
         if use_gt_layout and isinstance(gt_layout, np.ndarray):
             tokens = np.ascontiguousarray(gt_layout, np.int32)
             packed, validity = self.assembler.assemble_packed(tokens)

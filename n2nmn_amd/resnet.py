@@ -43,7 +43,7 @@ from typing import Dict, List, Sequence, Tuple
 
 import numpy as np
 
-from . import _lib
+from . import _lib, feed
 from .vgg_net import channel_mean, _read_rgb
 
 BLOCKS_152: Tuple[int, int, int, int] = (3, 8, 36, 3)
@@ -253,11 +253,12 @@ class ResNetRes5c:
             t = t.to(torch.float32)
         return t.to(self.device).contiguous()
 
-    def forward(self, images):
+    def forward(self, images, out_dtype=None):
         """images: uint8 or float [N, H, W, 3] RAW pixel values (host or device; the channel mean is subtracted by
         the first kernel) -> float32 DEVICE tensor [N, h, w, 32 base_width] on the current stream (448 x 448 ->
         14 x 14 x 2048).  Nothing is copied to the host: hand the result to VQAEngine.forward as image_feat_batch.
-        Before load_weights the library refuses (N2NMN_ENOWEIGHT)."""
+        Before load_weights the library refuses (N2NMN_ENOWEIGHT).  out_dtype='float16': the grid narrowed to IEEE
+        half on the device (n2nmn_features_narrow, round to nearest even)."""
         import torch
         t = self._images(images)
         N, H, W, _ = t.shape
@@ -265,7 +266,7 @@ class ResNetRes5c:
         with torch.cuda.device(self.device):
             _lib.check(self._lib.n2nmn_resnet_forward(self._h, t.data_ptr(), 1 if t.dtype == torch.uint8 else 0,
                                                       N, H, W, out.data_ptr(), self.stream()))
-        return out
+        return feed.narrow(out) if feed.half_requested(out_dtype) else out
 
     def layer(self, name: str):
         """Dense device copy [N, h, w, C] of one layer's output for the last forward's images: 'conv1', 'pool1',
@@ -357,10 +358,11 @@ def _read_resized(path: str, size: int) -> np.ndarray:
 
 
 def extract_dataset_res5c(image_dir: str, save_dir: str, ext_filter: str = '*.jpg', net: ResNetRes5c = None,
-                          size: int = 448, batch_size: int = 8, verbose: bool = False) -> int:
+                          size: int = 448, batch_size: int = 8, verbose: bool = False, dtype=None) -> int:
     """For every image matching `ext_filter` in `image_dir`, one `<image name>.npy` in `save_dir` holding the
     features as float32 (1, size/32, size/32, 2048) -- the `feature_path` build_vqa_imdb.py:53 records; files that
-    exist are skipped.  size = 0 keeps each image's own extent.  Returns the number of files written."""
+    exist are skipped.  size = 0 keeps each image's own extent.  dtype='float16': float16 files of the same shape,
+    narrowed on the device.  Returns the number of files written."""
     if net is None:
         raise ValueError('extract_dataset_res5c: pass a ResNetRes5c with its weights loaded')
     os.makedirs(save_dir, exist_ok=True)
@@ -377,7 +379,7 @@ def extract_dataset_res5c(image_dir: str, save_dir: str, ext_filter: str = '*.jp
         nonlocal written
         if not pending:
             return
-        feat = net.forward(np.stack([im for _, im in pending])).cpu().numpy()
+        feat = net.forward(np.stack([im for _, im in pending]), out_dtype=dtype).cpu().numpy()
         for i, (save_path, _) in enumerate(pending):
             np.save(save_path, feat[i:i + 1])
             written += 1
@@ -407,6 +409,7 @@ def parse_args(argv=None):
     ap.add_argument('--mean', type=float, nargs=3, default=[float(x) for x in channel_mean],
                     help='per-channel mean in the order of the image channels')
     ap.add_argument('--device', type=int, default=0)
+    ap.add_argument('--dtype', choices=('float32', 'float16'), default='float32', help='container of the .npy files')
     a = ap.parse_args(argv)
     if a.size < 1 or a.batch < 1:
         ap.error('--size and --batch must be positive')
@@ -418,7 +421,7 @@ def main(argv=None):
     weights = load_npz(a.weights, bgr_conv1=a.bgr_conv1)
     net = ResNetRes5c(max_N=a.batch, max_H=a.size, max_W=a.size, channel_mean=a.mean, device=a.device)
     net.load_weights(weights)
-    n = extract_dataset_res5c(a.images, a.out, a.ext, net=net, size=a.size, batch_size=a.batch, verbose=True)
+    n = extract_dataset_res5c(a.images, a.out, a.ext, net=net, size=a.size, batch_size=a.batch, verbose=True, dtype=a.dtype)
     print('wrote %d files to %s' % (n, a.out))
 
 

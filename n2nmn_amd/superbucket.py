@@ -25,6 +25,7 @@ from typing import Optional
 
 import numpy as np
 
+from . import feed
 from .engine import Engine, _torch
 from .nmn3_assembler import Assembler
 from .spec import Dims
@@ -87,11 +88,19 @@ class SuperBucket:
 
     def fill(self, k: int, batch, gt_layout=None):
         """Copy a client batch (numpy or tensors, any device) into slot k; asynchronous on the
-        current stream for device tensors."""
+        current stream for device tensors.  A compact batch (n2nmn_amd.feed: float16 features and / or an
+        `image_index_batch` into U <= Nb feature rows) crosses the link as it is and is expanded into the
+        slot's float32 grid on the current stream (Engine.features)."""
         torch = _torch()
         v = self.slot(k)
-        for key in ('input_seq_batch', 'seq_length_batch', 'image_feat_batch'):
+        compact = feed.is_compact(batch)
+        for key in ('input_seq_batch', 'seq_length_batch') + (() if compact else ('image_feat_batch',)):
             v[key].copy_(torch.as_tensor(batch[key]), non_blocking=True)
+        if compact:
+            src, index, n = self.engine.feature_source(batch['image_feat_batch'], batch.get('image_index_batch'))
+            if n > self.Nb:
+                raise ValueError('%d questions do not fit a slot of %d' % (n, self.Nb))
+            feed.expand(src, index, v['image_feat_batch'][:n])
         lens = batch['seq_length_batch']
         self._len_known[k] = isinstance(lens, np.ndarray)
         if self._len_known[k]:

@@ -25,7 +25,7 @@ from typing import Dict, List, Tuple
 
 import numpy as np
 
-from . import _lib
+from . import _lib, feed
 
 channel_mean = np.array([123.68, 116.779, 103.939], dtype=np.float32)      # vgg_net.py:14
 
@@ -148,10 +148,12 @@ class VGGPool5:
             t = t.to(torch.float32)
         return t.to(self.device).contiguous()
 
-    def forward(self, images):
+    def forward(self, images, out_dtype=None):
         """images: uint8 or float [N, H, W, 3] RAW RGB values (host or device; channel_mean is subtracted by the
         first kernel) -> float32 DEVICE tensor [N, ceil(H/32), ceil(W/32), 512] on the current stream.  Nothing is
-        copied to the host: hand the result to Engine / NMN3Model / the super-bucket feeder as image_feat."""
+        copied to the host: hand the result to Engine / NMN3Model / the super-bucket feeder as image_feat.
+        out_dtype='float16': the grid narrowed to IEEE half on the device (n2nmn_features_narrow, round to nearest
+        even): half the D2H copy and half the file of an extraction run; Engine takes it as it is."""
         import torch
         if not self._loaded:
             raise RuntimeError('vgg_net: no weights loaded (load_weights / load_checkpoint)')
@@ -161,7 +163,7 @@ class VGGPool5:
         with torch.cuda.device(self.device):
             _lib.check(self._lib.n2nmn_vgg_forward(self._h, t.data_ptr(), 1 if t.dtype == torch.uint8 else 0,
                                                    N, H, W, out.data_ptr(), self.stream()))
-        return out
+        return feed.narrow(out) if feed.half_requested(out_dtype) else out
 
     def layer(self, name: str):
         """Dense device copy [N, h, w, C] of one layer's activation (after ReLU) of the last forward."""
@@ -225,9 +227,11 @@ def _read_rgb(path: str) -> np.ndarray:
 
 
 def extract_dataset_pool5(image_dir: str, save_dir: str, ext_filter: str = '*.png', vgg: VGGPool5 = None,
-                          batch_size: int = 8, verbose: bool = False) -> int:
+                          batch_size: int = 8, verbose: bool = False, dtype=None) -> int:
     """The reference script's contract: for every image matching `ext_filter` in `image_dir`, one
     `<image name>.npy` in `save_dir` holding pool5 as float32 (1, H/32, W/32, 512); files that exist are skipped.
+    dtype='float16': float16 files of the same shape, narrowed on the device (DataReader's feature_dtype='float16'
+    loads them as they are).
     Consecutive images of equal size run as one batch of up to `batch_size` (the handle's max_N).  Returns the
     number of files written.  vgg: a loaded VGGPool5 (its max_N / max_H / max_W bound what can be read)."""
     if vgg is None:
@@ -247,7 +251,7 @@ def extract_dataset_pool5(image_dir: str, save_dir: str, ext_filter: str = '*.pn
         nonlocal written
         if not pending:
             return
-        feat = vgg.forward(np.stack([im for _, im in pending])).cpu().numpy()
+        feat = vgg.forward(np.stack([im for _, im in pending]), out_dtype=dtype).cpu().numpy()
         for i, (save_path, _) in enumerate(pending):
             np.save(save_path, feat[i:i + 1])
             written += 1
@@ -276,10 +280,11 @@ def main(argv=None):
     ap.add_argument('--width', type=int, default=480)
     ap.add_argument('--batch', type=int, default=8)
     ap.add_argument('--device', type=int, default=0)
+    ap.add_argument('--dtype', choices=('float32', 'float16'), default='float32', help='container of the .npy files')
     a = ap.parse_args(argv)
     vgg = VGGPool5(max_N=a.batch, max_H=a.height, max_W=a.width, device=a.device)
     vgg.load_checkpoint(a.weights, scope=a.scope)
-    n = extract_dataset_pool5(a.images, a.out, a.ext, vgg=vgg, batch_size=a.batch, verbose=True)
+    n = extract_dataset_pool5(a.images, a.out, a.ext, vgg=vgg, batch_size=a.batch, verbose=True, dtype=a.dtype)
     print('wrote %d files to %s' % (n, a.out))
 
 

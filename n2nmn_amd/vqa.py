@@ -26,7 +26,7 @@ from typing import Dict, Optional, Tuple
 
 import numpy as np
 
-from . import _lib
+from . import _lib, feed
 from .engine import Engine
 from .train import Trainer
 from .nmn3_assembler import Assembler
@@ -225,17 +225,34 @@ class VQAEngine:
                 return base
         return None
 
-    def features_with_coords(self, image_feat):
+    def fill_slab(self, slab_rows, image_feat, index=None):
+        """slab_rows[n, :, :, :D] = float(image_feat[index[n] if index is not None else n]) for whole rows of a
+        feature_slab() (n2nmn_features_expand with dst_pixel_stride = Dp): the coordinate channels and the padding
+        are not touched.  image_feat: [U, H, W, D] float32 or float16, host or device; index: int32 [n] (a host
+        array is checked before any device call), None for U rows as they are.  Asynchronous on the current
+        stream; returns slab_rows[:n]."""
+        d = self.dims
+        if not hasattr(slab_rows, 'data_ptr') or self._slab_of(slab_rows) is None:
+            raise ValueError('fill_slab: the destination must be whole rows of a feature_slab() that is still alive')
+        src, index, n = self.engine.feature_source(image_feat, index)
+        if n > slab_rows.shape[0] or tuple(src.shape[1:]) != (d.H, d.W, d.D):
+            raise ValueError('fill_slab: %d rows of %s do not fit %s' % (n, tuple(src.shape[1:]), tuple(slab_rows.shape)))
+        return feed.expand(src, index, slab_rows[:n], D=d.D)
+
+    def features_with_coords(self, image_feat, index=None):
         """[N,H,W,D] image features -> [N,H,W,Dp] with the coordinate map appended (on the GPU); a slab
-        of `feature_slab` already has it and is returned as it is."""
+        of `feature_slab` already has it and is returned as it is.  float16 features and / or an image `index`
+        (Engine.features) are widened / gathered on the device first."""
         import torch
         e, d, di = self.engine, self.dims, self.idims
         if hasattr(image_feat, 'data_ptr') and image_feat.dim() == 4 and image_feat.shape[-1] == di.D != d.D:
+            if index is not None:
+                raise ValueError('a slab already holds one row per question: fill it with fill_slab(rows, feat, index)')
             if self._slab_of(image_feat) is None:
                 raise ValueError('a [N, H, W, %d] tensor must be a slab of feature_slab() that is still alive (or whole '
                                  'rows of one); raw image features are [N, H, W, %d]' % (di.D, d.D))
             return image_feat
-        feat = e._dev(image_feat, torch.float32)
+        feat = e.features(image_feat, index)
         n = feat.shape[0]
         if self._feat_c is None or self._feat_c.shape[0] != n:
             self._feat_c = torch.empty((n, di.H, di.W, di.D), dtype=torch.float32, device=e.device)
@@ -281,7 +298,7 @@ class VQAEngine:
         s2s = e.seq2seq(batch['input_seq_batch'], batch['seq_length_batch'], self.dims.T_decoder,
                         use_gt_layout, gt_dev if known else gt_layout, None, forced_tokens,
                         eos_retire=retire, gt_len_host=e.layout_lengths(tokens) if (retire and known) else None)
-        feat_c = self.features_with_coords(batch['image_feat_batch'])
+        feat_c = self.features_with_coords(batch['image_feat_batch'], batch.get('image_index_batch'))
         if known or host_assemble:
             if not known:
                 tokens = s2s['predicted_tokens'].cpu().numpy()
